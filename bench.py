@@ -3,6 +3,7 @@
 one U-Net training epoch) on synthetic data of a BASELINE.json shape.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak] [--config isic|suim|cityscapes|hela] [--alpha A]
+                    [--dump-outputs DIR]
 
 Default = the configuration the metric is quoted on (BASELINE.json configs[1]): ISIC-2018-shaped 256x256x3, 2-model
 ensemble, alpha = 0.5.  --config picks one of the other shapes (configs[2..4]); --alpha overrides the width (the IM+
@@ -178,6 +179,51 @@ def write_detail(full, path=None):
         except OSError:
             continue
     return None
+
+
+DUMP_BUDGET = 64 << 20      # bytes of all --dump-outputs files together
+DUMP_IMAGES = 16            # images of the set whose blocked image, pseudo-label and IM are written
+DUMP_PARAMS = 4 << 20       # student parameters written whole up to this count, a fixed sample of this many above it
+
+
+def dump_outputs(path, n_unl, pool_x, pool_y, last_gen, student):
+    """--dump-outputs: what the timed path computed in its LAST generation, as <path>/<name>.npy (float32, float64 for the int64
+    sizes).  Per image of the set: pred_size, im_size [U,Kb], keep [U]; for a fixed sample of DUMP_IMAGES images (sample_index):
+    the blocked image img_out [S,H,W,C], the pseudo-label masks [S,Kb,H,W] and the IM [S,H,W]; the student after its epoch:
+    student_params (flat, fp32: weights + BatchNorm moving statistics; a fixed sample above DUMP_PARAMS, positions in
+    student_params_index) and student_stats (the last training step's statistics).  The samples are seeded, so two runs with the same
+    arguments write the same positions.  Returns (files, bytes)."""
+    rng = np.random.default_rng(20240601)
+    sel = np.sort(rng.choice(n_unl, min(n_unl, DUMP_IMAGES), replace=False))
+    batches = last_gen["batches"]
+    starts = np.array([i for i, _ in batches])
+    im = []
+    for s in sel:
+        b = int(np.searchsorted(starts, s, side="right")) - 1
+        i, r = batches[b]
+        im.append(r["im"][int(s) - i].cpu().numpy())
+    sel_t = torch.from_numpy(sel).to(pool_x.device)
+    out = {"pred_size": torch.cat([r["pred_size"] for _, r in batches]).cpu().numpy().astype(np.float64),
+           "im_size": torch.cat([r["im_size"] for _, r in batches]).cpu().numpy().astype(np.float64),
+           "keep": last_gen["keep"].cpu().numpy().astype(np.float32),
+           "sample_index": sel.astype(np.float64),
+           "img_out": pool_x[sel_t].cpu().numpy().astype(np.float32),
+           "masks": pool_y[sel_t].cpu().numpy().astype(np.float32),
+           "im": np.stack(im).astype(np.float32),
+           "student_stats": student.stats.cpu().numpy().astype(np.float32)}
+    params = student.params.cpu().numpy().astype(np.float32)
+    if params.size > DUMP_PARAMS:
+        pi = np.sort(np.random.default_rng(20240602).choice(params.size, DUMP_PARAMS, replace=False))
+        out["student_params_index"] = pi.astype(np.float64)
+        params = params[pi]
+    out["student_params"] = params
+    assert out["pred_size"].shape[0] == n_unl and out["keep"].shape[0] == n_unl
+    total = sum(a.nbytes for a in out.values())
+    assert total <= DUMP_BUDGET, f"--dump-outputs would write {total} bytes"
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return len(out), total
 
 
 def synth_images(cfg, n, seed, device):
@@ -512,6 +558,10 @@ def main():
     ap.add_argument("--detail", default=None, help="where the full record goes (default gpurun_out/bench_detail[_<config>].json)")
     ap.add_argument("--provenance", action="store_true",
                     help="print {bench_py_sha16, lib_build_id} (what profiles/collect_round.sh records beside the files it cuts) and exit")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (sizes, keep rule, a fixed sample of blocked images / "
+                         "pseudo-labels / IMs, the trained student's parameters) as DIR/<name>.npy, e.g. DIR = bench_outputs/<build> (rank 0, "
+                         "the requested configuration only)")
     ap.add_argument("--no-other-configs", action="store_true",
                     help="default run (isic, 1 GPU) only: skip the short runs of the other BASELINE shapes appended as other_configs")
     args = ap.parse_args()
@@ -685,6 +735,10 @@ def run_config(args, config_name, alpha, env, primary):
     steps_cap = torch.zeros(1, dtype=torch.int64, device=dev)
 
     infer_batches = lambda n: F.infer_batches(n, infer_batch)      # a short last call is spread over the others (functions.infer_batches)
+    # --dump-outputs: the ensemble's per-batch results and the keep rule of the latest generation stay referenced (nothing is copied
+    # inside the timed region); dump_outputs reads them after it
+    dump = primary and rank == 0 and args.dump_outputs is not None
+    last_gen = {}
 
     def im_stage(x, into_pool=True):
         ps, ims = [], []
@@ -692,6 +746,8 @@ def run_config(args, config_name, alpha, env, primary):
             r = ens.run(x[i:j], cfg["thr"], cfg["cmp_ge"], True, True,
                         out={"img_out": pool_x[i:j], "masks": pool_y[i:j]} if into_pool else None)
             ps.append(r["pred_size"].sum(1)); ims.append(r["im_size"].sum(1))
+            if dump and into_pool:
+                last_gen["batches"].append((i, r))
         ps, ims = torch.cat(ps), torch.cat(ims)
         keep = ((ps > ims) & (ps > 0)) if cfg["keep_rule"] else torch.ones_like(ps, dtype=torch.bool)   # functions.py:2878-2886 (ISIC only)
         return ps, ims, keep
@@ -704,10 +760,15 @@ def run_config(args, config_name, alpha, env, primary):
 
     def generation(record=None):
         e0, e1, e2 = ev(), ev(), ev()
+        if dump:
+            last_gen.clear()
+            last_gen["batches"] = []
         if stage_marks[0]:
             Profiler.mark(4)
         e0.record()
         ps, ims, keep = im_stage(x_unl)
+        if dump:
+            last_gen["keep"] = keep
         e1.record()
         if stage_marks[0]:
             Profiler.mark(3)
@@ -792,6 +853,11 @@ def run_config(args, config_name, alpha, env, primary):
         prof.totals(False)
     pc, pms, pby, pfl = prof_collect()
     prof.set_period(0)
+    if dump:        # before anything below runs the student or the IM stage again
+        n_files, n_bytes = dump_outputs(args.dump_outputs, U, pool_x, pool_y, last_gen, student)
+        print(f"[bench] outputs of the last timed step: {n_files} files, {n_bytes / 2**20:.1f} MB in {args.dump_outputs}",
+              file=sys.stderr, flush=True)
+        last_gen.clear()
     if primary and not args.no_prof:
         # which kernel variants make up which stage (launches and algorithmic bytes per generation): one more generation, outside
         # the clock, with the library's totals read at the stage boundary (host-side sums: no synchronisation involved)

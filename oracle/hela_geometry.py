@@ -9,7 +9,7 @@ container, so the reference cannot run them here): restated from the published a
 tests/test_cpu_second_opinion.py (centre of mass, Euclidean disc areas).  get_min_dist and get_cell_count are plain numpy in the
 reference and are pinned by tests/golden (make_golden.py imports the reference).
 
-Reference lines followed (relative to /root/reference): functions.py:6181-6218 get_pos_contours, 6221-6252 get_min_dist,
+Reference lines followed (relative to the reference checkout): functions.py:6181-6218 get_pos_contours, 6221-6252 get_min_dist,
 6255-6292 mod_pos_size, 6298-6371 get_cell_count."""
 import numpy as np
 

@@ -6,7 +6,7 @@
  *
  * Parity status: PINNED -- tests/test_oracle_golden.py runs every golden case through this file.
  *
- * Reference lines followed (relative to /root/reference):
+ * Reference lines followed (relative to the reference checkout):
  *   functions.py:3104-3120  binary: s = sum of votes; final = (s==N); im = (s!=0 && s!=N)
  *   functions.py:3157       ISIC vote  = p >  thr        functions.py:3187-3189  HeLa vote = p >= thr
  *   functions.py:3195-3200  HeLa: combined IM = max over channels, im_size = sum over channels

@@ -10,7 +10,7 @@ Parity status: PINNED.  tests/test_oracle_golden.py checks every function below 
 tests/golden/*.npz, which tests/golden/make_golden.py produced by importing the real
 reference (functions.py) in the build container.
 
-Reference lines followed (relative to /root/reference):
+Reference lines followed (relative to the reference checkout):
   binary core      functions.py:3104-3120  pred_masks_to_im_binary
   binary caller    functions.py:3155-3160  get_im_prediction_binary   (strict  `> thr`)
   HeLa caller      functions.py:3183-3200  get_im_prediction_hela     (`>= thr`, max of IMs, sum of sizes)

@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
 """Generate golden vectors for the IM hot path by importing the REAL reference.
 
-Run ONLY in the build container (needs /root/reference):
+Run where a checkout of the reference is on disk:
 
-    python tests/golden/make_golden.py
+    IMK_REFERENCE=/path/to/InconsistencyMasks python tests/golden/make_golden.py
+
+It also rewrites tests/golden/digests.json (a sha256 per array of every fixture), which
+tests/test_golden_regenerate.py holds the committed fixtures to.
 
 The reference module `functions.py` imports cv2 / tensorflow / tensorflow_addons at
 the top (functions.py:7,10,11), none of which exist here.  We inject empty stub
@@ -34,8 +37,28 @@ import types
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-OUT = os.environ.get("IMK_GOLDEN_OUT", HERE)       # tests/test_golden_regenerate.py writes to a scratch directory and compares
-REF = "/root/reference"
+OUT = os.environ.get("IMK_GOLDEN_OUT", HERE)       # a scratch directory: compare a regeneration with the committed files first
+REF = os.environ.get("IMK_REFERENCE")
+FIXTURES = ("im_binary", "im_hela", "im_multiclass", "writer_isic", "writer_multi", "metrics", "augment", "evalnet_labels")
+
+
+def array_digest(a):
+    """sha256 over dtype, shape and bytes of one array (the form tests/test_golden_regenerate.py recomputes)"""
+    a = np.ascontiguousarray(a)
+    h = hashlib.sha256(f"{a.dtype.str}|{a.shape}|".encode())
+    h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def write_digests():
+    import json
+    rec = {}
+    for name in FIXTURES:
+        with np.load(os.path.join(OUT, name + ".npz")) as d:
+            rec[name] = {k: array_digest(d[k]) for k in sorted(d.files)}
+    with open(os.path.join(OUT, "digests.json"), "w") as f:
+        json.dump(rec, f, indent=1, sort_keys=True)
+        f.write("\n")
 
 
 def _stub(name):
@@ -429,6 +452,8 @@ def gen_evalnet_labels(F):
 
 
 if __name__ == "__main__":
+    if not REF or not os.path.exists(os.path.join(REF, "functions.py")):
+        sys.exit("set IMK_REFERENCE to a checkout of the reference (the directory that holds functions.py)")
     F, cv2 = import_reference()
     only = set(sys.argv[1:])          # e.g. `make_golden.py evalnet_labels` regenerates one file
     gens = [("binary", lambda: gen_binary(F)), ("hela", lambda: gen_hela(F)), ("multiclass", lambda: gen_multiclass(F)),
@@ -438,3 +463,4 @@ if __name__ == "__main__":
         for name, fn in gens:
             if not only or name in only:
                 fn()
+    write_digests()

@@ -593,6 +593,45 @@ def test_bench_replay_provenance(tmp_path, monkeypatch):
     assert not ok and "lib_build_id" in why
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.py --dump-outputs on CPU stand-ins for the last generation: one float32 / float64 .npy per output, the per-image arrays
+    whole, the sampled images and parameters taken at the same seeded positions every time, the whole dump under 64 MB."""
+    import types
+    sys.path.insert(0, ROOT)
+    import bench
+    torch = pytest.importorskip("torch")
+    U, H, W, C, KB = 100, 8, 12, 3, 3
+    g = torch.Generator().manual_seed(0)
+    pool_x = torch.randint(0, 256, (U + 7, H, W, C), generator=g, dtype=torch.uint8)
+    pool_y = torch.randint(0, 256, (U + 7, KB, H, W), generator=g, dtype=torch.uint8)
+    batches = []
+    for i, j in ((0, 40), (40, 80), (80, 100)):
+        batches.append((i, {"im": torch.full((j - i, H, W), 0, dtype=torch.uint8) + torch.arange(i, j, dtype=torch.uint8)[:, None, None],
+                            "pred_size": torch.arange(i, j).repeat(KB, 1).T * 7, "im_size": torch.arange(i, j).repeat(KB, 1).T}))
+    keep = torch.arange(U) % 3 != 0
+    student = types.SimpleNamespace(params=torch.randn(5000, generator=g), stats=torch.tensor([0.25, 0.0, 1.0]))
+    n, total = bench.dump_outputs(str(tmp_path / "a"), U, pool_x, pool_y, {"batches": batches, "keep": keep}, student)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert n == len(files) == 9 and all(f.endswith(".npy") for f in files) and total <= 64 << 20
+    d = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values())
+    sel = d["sample_index"].astype(np.int64)
+    assert len(sel) == bench.DUMP_IMAGES and np.all(np.diff(sel) > 0) and sel.max() < U
+    assert np.array_equal(d["img_out"], pool_x[sel].numpy()) and np.array_equal(d["masks"], pool_y[sel].numpy())
+    assert np.array_equal(d["im"][:, 0, 0], sel)                       # each sampled image's IM from the batch that holds it
+    assert np.array_equal(d["pred_size"][:, 0], np.arange(U) * 7) and d["im_size"].shape == (U, KB)
+    assert np.array_equal(d["keep"], keep.numpy()) and np.array_equal(d["student_params"], student.params.numpy())
+    assert np.array_equal(d["student_stats"], [0.25, 0.0, 1.0])
+    # a parameter vector above the cap: a fixed sample, its positions written beside it
+    monkeypatch.setattr(bench, "DUMP_PARAMS", 1000)
+    for sub in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / sub), U, pool_x, pool_y, {"batches": batches, "keep": keep}, student)
+    pi = np.load(tmp_path / "b" / "student_params_index.npy").astype(np.int64)
+    assert len(pi) == 1000 and np.array_equal(np.load(tmp_path / "b" / "student_params.npy"), student.params.numpy()[pi])
+    for f in os.listdir(tmp_path / "b"):
+        assert np.array_equal(np.load(tmp_path / "b" / f), np.load(tmp_path / "c" / f)), f
+
+
 def test_infer_batch_rule():
     from inconsistencymasks_amd import functions as F
     assert F.infer_batch_size(0.5) == 584 and F.infer_batch_size(1.0) == 128 and F.infer_batch_size(2.0, 64) == 64

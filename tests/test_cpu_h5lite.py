@@ -55,9 +55,7 @@ def test_latest_format_taken_or_refused_by_name():
 
 
 def test_matlab_v73_file_with_user_block():
-    p = "/usr/local/lib/python3.10/dist-packages/scipy/io/matlab/tests/data/testhdf5_7.4_GLNX86.mat"
-    if not os.path.exists(p):
-        pytest.skip("scipy's test data are not installed")
+    p = os.path.join(GOLD, "testhdf5_7.4_GLNX86.mat")                # SciPy's test file of the same name (BSD-3-Clause), 4 KB
     f = H.File(p)                                                    # written by MATLAB: a 512-byte user block in front
     assert np.allclose(np.asarray(f["testdouble"][...]).ravel(), np.arange(9) * np.pi / 4)
 

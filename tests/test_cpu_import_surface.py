@@ -1,7 +1,8 @@
 """The drop-in's REAL import surface (missing 2): for every reference script that has a counterpart under ISIC_2018/
 HeLa/ SUIM/ Cityscapes/, every name the reference script takes from `functions`, `unet`, `evalnet`, `paths`, the per-dataset class
-mappings and the TensorFlow namespace must resolve against the repo-root shims + inconsistencymasks_amd/compat.  Build container only
-(the reference is absent on the GPU box); the test reads NAMES out of the reference scripts' syntax trees and copies nothing.
+mappings and the TensorFlow namespace must resolve against the repo-root shims + inconsistencymasks_amd/compat.  The names were read
+out of the reference scripts' syntax trees into tests/golden/reference_surface.json (tools/dump_reference_surface.py --reference
+<checkout>; names and table values only, no source text), so the test needs nothing outside this repository.
 Reference: functions.py:105-160 (`ignore_im_*`), Cityscapes/13_Cityscapes_aug_IM+.py:6, HeLa/12_HeLa_IM++.py:5, HeLa/14_HeLa_aug_IM++.py:5."""
 import ast
 import json
@@ -12,72 +13,23 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+SURFACE = os.path.join(ROOT, "tests", "golden", "reference_surface.json")
 DATASETS = ("ISIC_2018", "HeLa", "SUIM", "Cityscapes")
-SHIMMED = {"functions", "unet", "evalnet", "paths", "SUIM_class_mapping", "Cityscapes_class_mapping"}
-TF_ROOTS = {"tf", "tensorflow", "mixed_precision", "keras", "K"}
 
 
-def _dotted(node):
-    parts = []
-    while isinstance(node, ast.Attribute):
-        parts.append(node.attr)
-        node = node.value
-    if isinstance(node, ast.Name):
-        parts.append(node.id)
-        return ".".join(reversed(parts))
-    return None
+def _surface():
+    with open(SURFACE) as f:
+        return json.load(f)
 
 
-def surface(path):
-    """-> (from-imports {module: {names}}, attribute chains rooted at an imported module alias {alias: {dotted}}, alias -> module)"""
-    tree = ast.parse(open(path, encoding="utf-8", errors="replace").read())
-    froms, alias = {}, {}
-    for n in ast.walk(tree):
-        if isinstance(n, ast.ImportFrom) and n.module:
-            froms.setdefault(n.module, set()).update(a.name for a in n.names)
-            for a in n.names:
-                alias[a.asname or a.name] = f"{n.module}.{a.name}"
-        elif isinstance(n, ast.Import):
-            for a in n.names:
-                alias[a.asname or a.name.split(".")[0]] = a.name if a.asname else a.name.split(".")[0]
-    chains = {}
-    for n in ast.walk(tree):
-        if isinstance(n, ast.Attribute):
-            d = _dotted(n)
-            if d and d.split(".")[0] in alias:
-                chains.setdefault(d.split(".")[0], set()).add(d)
-    return froms, chains, alias
-
-
-def pairs():
-    out = []
-    for ds in DATASETS:
-        for f in sorted(os.listdir(os.path.join(ROOT, ds))):
-            if f.endswith(".py") and os.path.exists(os.path.join(REF, ds, f)):
-                out.append((ds, f))
-    return out
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference is only present in the build container")
 def test_every_name_the_in_scope_reference_scripts_import_resolves():
-    ps = pairs()
+    rec = _surface()
+    ps = rec["scripts"]
     assert len(ps) >= 29, ps
-    wanted = {}     # "module:name" or "chain:<dotted, module-qualified>" -> scripts that need it
-    for ds, f in ps:
-        froms, chains, alias = surface(os.path.join(REF, ds, f))
-        for mod, names in froms.items():
-            top = mod.split(".")[0]
-            if top in SHIMMED or top in ("tensorflow", "tensorflow_addons"):
-                for n in names:
-                    wanted.setdefault(f"from:{mod}:{n}", []).append(f"{ds}/{f}")
-        for a, ds_ in chains.items():
-            target = alias[a].split(".")[0]
-            if target in SHIMMED or target in ("tensorflow", "tensorflow_addons"):
-                # keep the longest chains only (tf.keras.models.load_model implies tf.keras.models)
-                longest = {d for d in ds_ if not any(o != d and o.startswith(d + ".") for o in ds_)}
-                for d in longest:
-                    wanted.setdefault(f"chain:{alias[a]}:{d.split('.', 1)[1]}", []).append(f"{ds}/{f}")
+    missing_scripts = [p for p in ps if not os.path.exists(os.path.join(ROOT, p))]
+    assert not missing_scripts, missing_scripts           # every recorded reference script still has its counterpart here
+    wanted = rec["wanted"]     # "from:module:name" or "chain:<module>:<dotted>" -> scripts that need it
+    assert all(set(v) <= set(ps) for v in wanted.values())
     assert any(k.endswith(":ignore_im_categorical_crossentropy") for k in wanted)      # the gap round 5's hand-written script could not see
     assert any(k.startswith("chain:paths:") for k in wanted) and any("load_model" in k for k in wanted)
     probe = r"""
@@ -136,10 +88,9 @@ def test_ignore_im_losses_are_importable_and_refused_by_the_trainers():
             F.train_multiclass(*([None] * 10), loss, *([None] * 9))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference is only present in the build container")
 def test_generated_colour_tables_equal_the_reference_modules():
     """SUIM/SUIM_class_mapping.py and Cityscapes/Cityscapes_class_mapping.py here GENERATE their tables from the public palettes' rules;
-    every name of the reference modules must come out equal."""
+    every name of the reference modules (recorded in tests/golden/reference_surface.json) must come out equal."""
     import importlib.util
 
     def load(path, name):
@@ -147,9 +98,10 @@ def test_generated_colour_tables_equal_the_reference_modules():
         m = importlib.util.module_from_spec(spec)
         spec.loader.exec_module(m)
         return m
+    tables = _surface()["class_tables"]
     for ds, mod in (("SUIM", "SUIM_class_mapping"), ("Cityscapes", "Cityscapes_class_mapping")):
-        mine, ref = load(os.path.join(ROOT, ds, mod + ".py"), "mine_" + mod), load(os.path.join(REF, ds, mod + ".py"), "ref_" + mod)
-        names = [n for n in vars(ref) if n.isupper()]
+        mine, ref = load(os.path.join(ROOT, ds, mod + ".py"), "mine_" + mod), tables[mod]
+        names = sorted(ref)
         assert len(names) >= 3
         for n in names:
-            assert getattr(mine, n) == getattr(ref, n), (mod, n)
+            assert getattr(mine, n) == ast.literal_eval(ref[n]), (mod, n)

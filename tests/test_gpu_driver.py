@@ -805,6 +805,31 @@ def test_bench_one_rank_process_group_rccl():
     assert "all_families" in full["roofline"] and "timed_region_kernel_totals" in full
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs DIR: the last timed generation's outputs as float32 / float64 .npy files under 64 MB -- the keep rule
+    recomputed from the dumped sizes, the kept count equal to the line's, blocked images / pseudo-labels / IMs of the sampled images in
+    range, the student's parameters finite."""
+    import json
+    out_dir = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--images", "96", "--labeled", "32", "--steps", "2",
+                        "--warmup", "1", "--pretrain-steps", "10", "--bn-settle-steps", "10", "--no-cpu-baseline", "--dump-outputs",
+                        str(out_dir)], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    assert out["steps"] == 2 and out["ms_per_step"] > 0
+    d = {f[:-4]: np.load(out_dir / f) for f in os.listdir(out_dir)}
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values()) and sum(a.nbytes for a in d.values()) <= 64 << 20
+    assert d["pred_size"].shape == d["im_size"].shape == (96, 1) and d["keep"].shape == (96,)
+    ps, ims = d["pred_size"][:, 0], d["im_size"][:, 0]
+    assert np.array_equal(d["keep"], ((ps > ims) & (ps > 0)).astype(np.float32))         # ISIC's keep rule
+    assert int(d["keep"].sum()) == out["config"]["kept"]                                   # the same generation as the line's
+    n = len(d["sample_index"])
+    assert n == 16 and d["img_out"].shape == (n, 256, 256, 3) and d["masks"].shape == (n, 1, 256, 256) and d["im"].shape == (n, 256, 256)
+    assert set(np.unique(d["masks"])) <= {0.0, 255.0} and d["img_out"].min() >= 0 and d["img_out"].max() <= 255
+    assert np.array_equal((d["im"] > 0).sum((1, 2)), ims[d["sample_index"].astype(np.int64)])
+    assert np.isfinite(d["student_params"]).all() and np.isfinite(d["student_stats"]).all()
+
+
 def test_bench_two_ranks_driver_command_form():
     """The driver's N > 1 command, literally (`python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1
     --master-port P bench.py --gpus 2 ...`), with both ranks time-slicing this box's one GPU over gloo (IMK_BENCH_ONE_GPU /

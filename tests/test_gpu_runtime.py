@@ -33,7 +33,28 @@ def test_unet_and_evalnet_plans_share_the_side_stream_pool():
             assert s.value
             got.append(s.value)
     assert got[0] == got[2] and got[1] == got[3] and got[0] != got[1]
-    assert lib.imk_runtime_warnings() == 0        # the package exported GPU_MAX_HW_QUEUES=8 before the runtime started
+    # a process whose caller chose no queue count: the package exported GPU_MAX_HW_QUEUES=8 before the runtime started, so a side
+    # stream raises no warning (a fresh child -- this one's count is whatever the environment running the suite chose)
+    env = {k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}
+    r = subprocess.run([sys.executable, "-c", CHILD_PACKAGE_HWQ, ROOT], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.strip().splitlines()[-1] == "WARN 0 8", r.stdout + r.stderr
+
+
+CHILD_PACKAGE_HWQ = textwrap.dedent("""
+    import ctypes, sys
+    sys.path.insert(0, sys.argv[1])
+    import inconsistencymasks_amd, os
+    import torch
+    from inconsistencymasks_amd._lib import check, lib
+    from inconsistencymasks_amd.unet import UNet
+    torch.cuda.set_device(0)
+    u = UNet(32, 32, 3, 1, 0.5, "sigmoid", seed=1)
+    s = ctypes.c_void_p()
+    check(lib.imk_unet_plan_side_stream(u.plan.ptr, 0, ctypes.byref(s)), "imk_unet_plan_side_stream")
+    assert s.value
+    print("WARN", lib.imk_runtime_warnings(), os.environ["GPU_MAX_HW_QUEUES"])
+""")
 
 
 CHILD_HWQ = textwrap.dedent("""

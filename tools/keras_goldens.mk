@@ -12,7 +12,7 @@
 # probabilities, losses, post-fit weights) plus a JSON string of the versions: nothing of the reference's source travels.
 # With the files present, `python -m pytest tests/test_gpu_keras_goldens.py -m gpu` checks the HIP path AND oracle/unet_oracle.py
 # against them (probabilities, every stored layer, 3 optimizer steps); DESIGN.md section 6 then drops "parity unpinned" for the U-Net.
-REFERENCE ?= /root/reference
+REFERENCE ?= $(error set REFERENCE=/path/to/InconsistencyMasks)
 VENV ?= .venv-keras-goldens
 PY ?= python3
 
