@@ -91,6 +91,29 @@ IMK_API int imk_morph(const uint8_t *src, uint8_t *dst, int batch, int h, int w,
 IMK_API int imk_block_apply(const uint8_t *im, uint8_t *img, int c, uint8_t *masks, int n_masks,
                     int batch, int h, int w, void *stream);
 
+/* Model-ensemble voting: the pseudo-label rules of the model-ensemble baseline (get_model_ensemble_prediction_*,
+ * functions.py:2409-2566), for a whole batch in one launch.  mode IMK_VOTE_HARD / IMK_VOTE_SOFT.
+ *   preds      [N,B,H,W,Kb] float32   probabilities of the N ensemble members
+ *   masks_out  [B,Kb,H,W] uint8 {0,255}
+ *     hard: 255 where every model has p > (float)thr: numpy compares the float32 predictions with the Python threshold in
+ *           float32 (get_model_ensemble_prediction_ISIC_2018, functions.py:2409-2435);
+ *     soft: 255 where ((double)p_0 + (double)p_1 + ...) / (double)N > thr, summed in model order with an IEEE fp64 divide and
+ *           compared in fp64 -- the float64 accumulator of get_model_ensemble_prediction_hela_soft (functions.py:2474-2528).
+ *           thr is a double so that thresholds that are not exact in fp32 (0.3) compare as the reference's Python float does.
+ *   NaN votes 0 (hard); it makes the soft average NaN, so the pixel is 0.                                              */
+enum { IMK_VOTE_HARD = 0, IMK_VOTE_SOFT = 1 };
+IMK_API int imk_vote_binary(const float *preds, int n_models, int batch, int h, int w, int kb, double thr, int mode,
+                    uint8_t *masks_out, void *stream);
+
+/* Multi-class model-ensemble vote.  probs [N,B,H,W,K] float32, K <= 64 -> final_out [B,H,W] uint8 class ids.
+ *   hard: the label where all N arg-maxes agree, else 0 (get_model_ensemble_prediction_multiclass_hard, functions.py:2438-2469);
+ *   soft: argmax_k fl32(fl32(((p_0k + p_1k) + p_2k) + ...) / N): fp32 sums in model order and a correctly rounded fp32
+ *         divide, what np.mean(axis=0) of the float32 stack computes (get_model_ensemble_prediction_multiclass_soft,
+ *         functions.py:2534-2566).
+ * Every arg-max is np.argmax's: the first maximum wins, and a NaN counts as the maximum (the first NaN wins).             */
+IMK_API int imk_vote_multiclass(const float *probs, int n_models, int batch, int h, int w, int k, int mode,
+                        uint8_t *final_out, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Tiny U-Net (unet.py:4-67): plan, parameters, forward, fused forward+IM, training step
  * ---------------------------------------------------------------------------------------------- */
@@ -177,6 +200,20 @@ IMK_API int imk_unet_forward_im(const imk_unet_plan *plan, int n_models,
                         uint8_t *img_out, uint8_t *masks_out, uint8_t *im_out,
                         int64_t *im_size, int64_t *pred_size, uint8_t *presence,
                         void *workspace, int64_t workspace_bytes, void *stream);
+
+/* Ensemble inference + model-ensemble vote: N models' forward passes, then head -> vote in ONE kernel that reads the N last
+ * decoder activations (fp16) and writes only the uint8 labels (softmax heads: the soft sums in a wave-private LDS slab).  The per-model probabilities come from the code of
+ * imk_unet_forward's head, so the outputs are bit-identical to imk_unet_forward x N + imk_vote_binary (sigmoid heads: masks_out
+ * [B,K,H,W]) / imk_vote_multiclass (softmax heads: masks_out [B,H,W]; thr unused).  mode IMK_VOTE_HARD / IMK_VOTE_SOFT.
+ * `params`/`packed` are arrays (host) of n_models device pointers.  Streams and workspace as imk_unet_forward_im: the workspace is
+ * sized by imk_unet_forward_im_workspace_bytes(plan, n_models, B, k), 1 <= k <= min(n_models, 3) concurrent streams.  Shapes the
+ * fused kernel does not cover (more than 8 models, sigmoid heads with more than 4 maps, last decoder widths other than 8, 16,
+ * 24 or 32 channels, a masks_out that is not 16-byte aligned) and plans with the materialize debug switch take the unfused route
+ * through the fp32 probability stack.                                                                              */
+IMK_API int imk_unet_forward_vote(const imk_unet_plan *plan, int n_models,
+                          const float *const *params, const void *const *packed,
+                          const uint8_t *x, int batch, double thr, int mode, uint8_t *masks_out,
+                          void *workspace, int64_t workspace_bytes, void *stream);
 
 /* Training (functions.py:207-218, one step of model.fit): forward with batch statistics, loss,
  * backward, optimizer.  Split in two so that a data-parallel caller can all-reduce `grads` in between.

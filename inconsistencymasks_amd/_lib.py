@@ -58,6 +58,10 @@ SIGNATURES = {
                                     c_void_p, c_int, c_float, c_int, c_void_p, c_int, c_int,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_int64, c_void_p]),
+    "imk_vote_binary": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_void_p]),
+    "imk_vote_multiclass": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "imk_unet_forward_vote": (c_int, [c_void_p, c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
+                                      c_void_p, c_int, ctypes.c_double, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "imk_unet_state_bytes": (c_int64, [c_void_p]),
     "imk_unet_state_init": (c_int, [c_void_p, c_void_p, c_void_p]),
     "imk_unet_fwd_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,

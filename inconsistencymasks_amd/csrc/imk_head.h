@@ -185,3 +185,18 @@ struct ImkHeadImArgs {
 // runs head_kernel per model + imk_im_binary / imk_im_multiclass).
 bool imk_head_im_supported(const ImkHeadImArgs &a);
 int imk_launch_head_im(const ImkHeadImArgs &a, hipStream_t stream);
+
+// ---- fused head + model-ensemble vote (imk_vote.hip) ----------------------------------------------------------------------
+struct ImkVoteHeadArgs {
+    const f16 *z[IMK_HEAD_IM_MAX_MODELS];        // last decoder block's conv output [B,H,W,cs] of every model
+    const float *sc[IMK_HEAD_IM_MAX_MODELS], *sh[IMK_HEAD_IM_MAX_MODELS];   // its folded BatchNorm
+    const float *w[IMK_HEAD_IM_MAX_MODELS], *bias[IMK_HEAD_IM_MAX_MODELS];  // the head's fp32 kernel [cin][K] / bias [K]
+    int n_models, cin, cs, K, softmax;
+    int batch, hw;
+    double thr;                                  // fp64 for the soft vote; the hard vote compares against (float)thr
+    int mode;                                    // IMK_VOTE_HARD / IMK_VOTE_SOFT
+    uint8_t *out;                                // masks [B,K,H,W] {0,255}
+};
+// Sigmoid heads in the shapes of imk_head_im_supported; the caller takes imk_unet_forward + imk_vote_* otherwise.
+bool imk_vote_head_supported(const ImkVoteHeadArgs &a);
+int imk_launch_vote_head(const ImkVoteHeadArgs &a, hipStream_t stream);

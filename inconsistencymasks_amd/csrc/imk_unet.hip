@@ -326,6 +326,59 @@ extern "C" int64_t imk_unet_forward_im_workspace_bytes(const imk_unet_plan *plan
     return (int64_t)(head_slab_bytes(plan, batch, true) * n_models + make_ws(plan, batch, 0).total * n_streams);
 }
 
+// Where the fused head of an ensemble finds each model: its last decoder activation and folded BatchNorm, its output layer.
+struct EnsembleHeads {
+    const f16 **z;
+    const float **sc, **sh, **w, **bias;
+};
+
+// The N forward passes of an ensemble (imk_unet_forward_im, imk_unet_forward_vote).  `slab` bytes per model at the start of the
+// workspace, then one activation workspace per concurrent stream.  heads != NULL (fused): the last decoder activation of model m goes
+// to its head slab and `heads` receives the pointers the fused kernel reads; no head launch.  heads == NULL: model m's fp32
+// probabilities go to base + m * B*H*W*K*4 (the contiguous stack [N,B,H,W,K]).  Everything ends joined to `main_stream`.
+static int run_ensemble_forwards(const imk_unet_plan *plan, const Topo &topo, const Ws &ws, int n_models, const float *const *params,
+                                 const void *const *packed, const uint8_t *x, int batch, size_t slab, uint8_t *base,
+                                 int64_t workspace_bytes, const EnsembleHeads *heads, hipStream_t main_stream) {
+    const imk_unet_cfg &cf = plan->cfg;
+    const bool fused = heads != nullptr;
+    // the unfused probability stack must be contiguous [N,B,H,W,K]: only the last slab may be padded
+    const size_t probs_exact = (size_t)batch * cf.h * cf.w * cf.n_out * sizeof(float);
+    // The models are independent until the IM stage: with room for one activation workspace per stream (the caller
+    // passes slabs + k * imk_unet_workspace_bytes, k <= 1 + MAX_SIDE) they run on k streams side by side -- the deep
+    // layers of one model fill the gaps of the other's.  With room for one only, they run back to back.
+    const int max_streams = 1 + imk_unet_plan::MAX_SIDE;
+    int n_slabs = (int)(((size_t)workspace_bytes - slab * n_models) / ws.total);
+    if (n_slabs > n_models) n_slabs = n_models;
+    if (n_slabs > max_streams) n_slabs = max_streams;
+    static const bool conc_off = []() { const char *e = getenv("IMK_ENSEMBLE_STREAMS"); return e && e[0] == '0'; }();
+    if (n_slabs > 1 && (conc_off || plan->dbg_single_stream || !ensure_side_streams(plan, n_slabs - 1))) n_slabs = 1;
+    if (n_slabs > 1) {
+        IMK_HIP(hipEventRecord(plan->ev_fork[0], main_stream));
+        for (int s = 1; s < n_slabs; ++s) IMK_HIP(hipStreamWaitEvent(plan->side[s - 1], plan->ev_fork[0], 0));
+    }
+    const ImkLayer &o = plan->layers[topo.out];
+    for (int m = 0; m < n_models; ++m) {
+        const int sl = m % n_slabs;
+        Ctx c{plan, ws, base + slab * n_models + ws.total * sl, params[m], (const uint8_t *)packed[m], batch, false,
+              sl == 0 ? main_stream : plan->side[sl - 1]};
+        c.x_in[0] = x;
+        if (fused) {    // the last decoder activation goes to the model's head slab; no head launch
+            c.ovr_conv = topo.d_c1[3];
+            c.ovr_out = reinterpret_cast<f16 *>(base + slab * m);
+            heads->z[m] = c.ovr_out;
+            heads->sc[m] = c.bn_scale(topo.d_bnb[3]); heads->sh[m] = c.bn_shift(topo.d_bnb[3]);
+            heads->w[m] = params[m] + o.off_w; heads->bias[m] = params[m] + o.off_b;
+        }
+        int rc = run_forward(c, topo, fused ? nullptr : (float *)(base + probs_exact * m), nullptr);
+        if (rc) return rc;
+    }
+    for (int s = 1; s < n_slabs; ++s) {
+        IMK_HIP(hipEventRecord(plan->ev_join[s - 1], plan->side[s - 1]));
+        IMK_HIP(hipStreamWaitEvent(main_stream, plan->ev_join[s - 1], 0));
+    }
+    return IMK_OK;
+}
+
 extern "C" int imk_unet_forward_im(const imk_unet_plan *plan, int n_models, const float *const *params,
                                    const void *const *packed, const uint8_t *x, int batch, float thr, int cmp_ge,
                                    const uint8_t *img, int block_in, int block_out, uint8_t *img_out, uint8_t *masks_out,
@@ -346,49 +399,47 @@ extern "C" int imk_unet_forward_im(const imk_unet_plan *plan, int n_models, cons
                  (int64_t)(head_slab_bytes(plan, batch, true) * n_models + ws.total) <= workspace_bytes;
     const size_t slab = head_slab_bytes(plan, batch, fused);
     if ((int64_t)(slab * n_models + ws.total) > workspace_bytes) return IMK_EWORKSPACE;
-    // the unfused probability stack must be contiguous [N,B,H,W,K]: only the last slab may be padded
-    const size_t probs_exact = (size_t)batch * cf.h * cf.w * cf.n_out * sizeof(float);
     uint8_t *base = (uint8_t *)workspace;
-    // The models are independent until the IM stage: with room for one activation workspace per stream (the caller
-    // passes slabs + k * imk_unet_workspace_bytes, k <= 1 + MAX_SIDE) they run on k streams side by side -- the deep
-    // layers of one model fill the gaps of the other's.  With room for one only, they run back to back.
-    const int max_streams = 1 + imk_unet_plan::MAX_SIDE;
-    int n_slabs = (int)(((size_t)workspace_bytes - slab * n_models) / ws.total);
-    if (n_slabs > n_models) n_slabs = n_models;
-    if (n_slabs > max_streams) n_slabs = max_streams;
-    static const bool conc_off = []() { const char *e = getenv("IMK_ENSEMBLE_STREAMS"); return e && e[0] == '0'; }();
-    if (n_slabs > 1 && (conc_off || plan->dbg_single_stream || !ensure_side_streams(plan, n_slabs - 1))) n_slabs = 1;
     hipStream_t main_stream = (hipStream_t)stream_;
-    if (n_slabs > 1) {
-        IMK_HIP(hipEventRecord(plan->ev_fork[0], main_stream));
-        for (int s = 1; s < n_slabs; ++s) IMK_HIP(hipStreamWaitEvent(plan->side[s - 1], plan->ev_fork[0], 0));
-    }
-    const ImkLayer &o = plan->layers[topo.out];
-    for (int m = 0; m < n_models; ++m) {
-        const int sl = m % n_slabs;
-        Ctx c{plan, ws, base + slab * n_models + ws.total * sl, params[m], (const uint8_t *)packed[m], batch, false,
-              sl == 0 ? main_stream : plan->side[sl - 1]};
-        c.x_in[0] = x;
-        if (fused) {    // the last decoder activation goes to the model's head slab; no head launch
-            c.ovr_conv = topo.d_c1[3];
-            c.ovr_out = reinterpret_cast<f16 *>(base + slab * m);
-            ha.z[m] = c.ovr_out;
-            ha.sc[m] = c.bn_scale(topo.d_bnb[3]); ha.sh[m] = c.bn_shift(topo.d_bnb[3]);
-            ha.w[m] = params[m] + o.off_w; ha.bias[m] = params[m] + o.off_b;
-        }
-        int rc = run_forward(c, topo, fused ? nullptr : (float *)(base + probs_exact * m), nullptr);
-        if (rc) return rc;
-    }
-    for (int s = 1; s < n_slabs; ++s) {
-        IMK_HIP(hipEventRecord(plan->ev_join[s - 1], plan->side[s - 1]));
-        IMK_HIP(hipStreamWaitEvent(main_stream, plan->ev_join[s - 1], 0));
-    }
+    const EnsembleHeads heads{ha.z, ha.sc, ha.sh, ha.w, ha.bias};
+    int rc = run_ensemble_forwards(plan, topo, ws, n_models, params, packed, x, batch, slab, base, workspace_bytes,
+                                   fused ? &heads : nullptr, main_stream);
+    if (rc) return rc;
     if (fused) return imk_launch_head_im(ha, main_stream);
     if (cf.act_out == 0)
         return imk_im_binary((const float *)base, n_models, batch, cf.h, cf.w, cf.n_out, thr, cmp_ge, img, cf.c_in, block_in,
                              block_out, img_out, masks_out, im_out, im_size, pred_size, stream_);
     return imk_im_multiclass((const float *)base, n_models, batch, cf.h, cf.w, cf.n_out, img, cf.c_in, block_in, block_out,
                              img_out, masks_out, im_out, im_size, presence, stream_);
+}
+
+// Ensemble inference + model-ensemble vote: the model loop of imk_unet_forward_im, then the fused head + vote kernel
+// (imk_vote.hip) on the activation slabs, or -- for the shapes it does not cover -- imk_vote_* on the probability stack.
+// Workspace: imk_unet_forward_im_workspace_bytes.
+extern "C" int imk_unet_forward_vote(const imk_unet_plan *plan, int n_models, const float *const *params,
+                                     const void *const *packed, const uint8_t *x, int batch, double thr, int mode,
+                                     uint8_t *masks_out, void *workspace, int64_t workspace_bytes, void *stream_) {
+    IMK_CHECK_ARG(plan && plan->net == 0 && params && packed && x && masks_out && workspace && batch > 0 && n_models > 0);
+    IMK_CHECK_ARG(mode == IMK_VOTE_HARD || mode == IMK_VOTE_SOFT);
+    const imk_unet_cfg &cf = plan->cfg;
+    const Ws ws = make_ws(plan, batch, 0);
+    const Topo topo = make_topo(plan);
+    ImkVoteHeadArgs va{};
+    va.n_models = n_models; va.cin = cf.ch[0]; va.cs = imk_pad8(cf.ch[0]); va.K = cf.n_out; va.softmax = cf.act_out;
+    va.batch = batch; va.hw = cf.h * cf.w; va.thr = thr; va.mode = mode; va.out = masks_out;
+    const bool fused = !plan->dbg_materialize && imk_vote_head_supported(va) &&
+                       (int64_t)(head_slab_bytes(plan, batch, true) * n_models + ws.total) <= workspace_bytes;
+    const size_t slab = head_slab_bytes(plan, batch, fused);
+    if ((int64_t)(slab * n_models + ws.total) > workspace_bytes) return IMK_EWORKSPACE;
+    uint8_t *base = (uint8_t *)workspace;
+    hipStream_t main_stream = (hipStream_t)stream_;
+    const EnsembleHeads heads{va.z, va.sc, va.sh, va.w, va.bias};
+    int rc = run_ensemble_forwards(plan, topo, ws, n_models, params, packed, x, batch, slab, base, workspace_bytes,
+                                   fused ? &heads : nullptr, main_stream);
+    if (rc) return rc;
+    if (fused) return imk_launch_vote_head(va, main_stream);
+    if (cf.act_out == 0) return imk_vote_binary((const float *)base, n_models, batch, cf.h, cf.w, cf.n_out, thr, mode, masks_out, stream_);
+    return imk_vote_multiclass((const float *)base, n_models, batch, cf.h, cf.w, cf.n_out, mode, masks_out, stream_);
 }
 
 // =====================================================================================================

@@ -24,6 +24,7 @@ from PIL import Image
 
 from . import evaluate as _ev
 from . import im as _im
+from . import vote as _vote
 from ._lib import check, lib
 from .unet import UNet, _stream
 
@@ -1436,6 +1437,94 @@ def create_pseudo_labels_im_hela(models, h, w, c, images_path, main_output_path,
     flush_writes()
     tot_im, tot_n = _all_reduce_sum([sum_im, count])
     return round(tot_im / tot_n, 0) if tot_n else 0.0
+
+
+# ---------------------------------------------------------------------------------------------------
+# Model-ensemble baseline (functions.py:1864-1990, 2409-2566): the N models' pseudo-label without an inconsistency mask.
+# The vote is imk_unet_forward_vote (native UNet models: head + vote fused, only the labels written) or imk_vote_* on the
+# stacked predictions of duck-typed `.predict` models (vote.py).
+# ---------------------------------------------------------------------------------------------------
+def get_model_ensemble_prediction_ISIC_2018(models, prepared_image, image_width, image_height, threshold):
+    """functions.py:2409-2435: 255 where every model has p > threshold.  float64 [image_width, image_height] in {0, 255}: the
+    reference returns its float64 vote sum."""
+    m = _vote.ensemble_vote(models, True).run(_prep(prepared_image)[:1], threshold, soft=False)
+    return m[0, 0].cpu().numpy().astype(np.float64).reshape(image_width, image_height)
+
+
+def get_model_ensemble_prediction_multiclass_hard(models, prepared_image):
+    """functions.py:2438-2469: the label where all N arg-maxes agree, else 0.  uint8 [H, W]."""
+    return _vote.ensemble_vote(models, False).run(_prep(prepared_image)[:1], soft=False)[0].cpu().numpy()
+
+
+def get_model_ensemble_prediction_multiclass_soft(models, prepared_image):
+    """functions.py:2534-2566: argmax of the fp32 mean of the N softmax maps.  uint8 [H, W]."""
+    return _vote.ensemble_vote(models, False).run(_prep(prepared_image)[:1], soft=True)[0].cpu().numpy()
+
+
+def _hela_vote_positions(temp_pos, max_pos_circle_size, min_pos_circle_size):
+    """functions.py:2515-2526: a filled circle per position blob of the thresholded mask, a lone cell drawn with distance 99;
+    [H, W, 3] like the reference's 3-channel canvas"""
+    pos = _redraw_positions(temp_pos, max_pos_circle_size, min_pos_circle_size, 99, 0)
+    return np.repeat(pos[..., None], 3, 2)
+
+
+def get_model_ensemble_prediction_hela_soft(models, prepared_image, threshold=0.5, max_pos_circle_size=8, min_pos_circle_size=3):
+    """functions.py:2474-2528: the fp64 mean of the N sigmoid maps > threshold per channel, then the position circles.
+    Returns (alive [H,W] u8, dead [H,W] u8, pos [H,W,3] u8), values 0 / 255."""
+    m = _vote.ensemble_vote(models, True).run(_prep(prepared_image)[:1], threshold, soft=True)[0].cpu().numpy()
+    return m[0], m[1], _hela_vote_positions(m[2], max_pos_circle_size, min_pos_circle_size)
+
+
+def _vote_out_dirs(main_output_path, subs):
+    out = {k: os.path.join(main_output_path, k) for k in subs}
+    for d in out.values():
+        os.makedirs(d, exist_ok=True)
+    return out
+
+
+def _run_vote_writer(models, images_path, c, binary, soft, threshold, flip_channels, per_image):
+    """Shared body of the model-ensemble writers: this rank's shard of the sorted file list in batches, one ensemble vote per
+    batch, the files of every image from per_image(name, image [H,W,C] as read, label rows) queued on the writer pool."""
+    mine = shard_list(os.listdir(images_path))
+    ens = _vote.ensemble_vote(models, binary)
+    with _pool() as pool:
+        for i, j in infer_batches(len(mine), infer_batch_size(_models_alpha(models))):
+            chunk = mine[i:j]
+            imgs = read_png_stack(pool, [os.path.join(images_path, n) for n in chunk], c)
+            x = torch.from_numpy(imgs).cuda()
+            if flip_channels:      # rgb=False: the nets see the file's channel order (functions.py:1890-1893)
+                x = x.flip(-1).contiguous()
+            lab = ens.run(x, threshold, soft).cpu().numpy()
+            jobs = [job for per in pool.map(lambda q: per_image(chunk[q], imgs[q], lab[q]), range(len(chunk))) for job in per]
+            write_pngs_async(jobs)      # encoded while the next batch is decoded and run
+    flush_writes()
+    d = _dist()
+    if d:      # every rank's files are on disk before rank 0 copies the labelled pairs in beside them (same names may occur)
+        d.barrier()
+
+
+def create_pseudo_labels_model_ensemble_ISIC_2018(models, images_path, main_output_path, h, w, c, rgb=True, threshold=0.5):
+    """functions.py:1864-1904: images/ (the image as read) and masks/ (255 where every model has p > threshold)."""
+    out = _vote_out_dirs(main_output_path, ("images", "masks"))
+    _run_vote_writer(models, images_path, c, True, False, threshold, not rgb and c == 3,
+                     lambda name, img, m: [(os.path.join(out["images"], name), img), (os.path.join(out["masks"], name), m[0])])
+
+
+def create_pseudo_labels_model_ensemble_multiclass(models, images_path, main_output_path, h, w, c, rgb=True):
+    """functions.py:1949-1990: images/ (the image as read) and masks/ (class ids of the soft vote)."""
+    out = _vote_out_dirs(main_output_path, ("images", "masks"))
+    _run_vote_writer(models, images_path, c, False, True, 0.5, not rgb and c == 3,
+                     lambda name, img, m: [(os.path.join(out["images"], name), img), (os.path.join(out["masks"], name), m)])
+
+
+def create_pseudo_labels_model_ensemble_hela(models, bf_images_path, main_output_path, h, w, c):
+    """functions.py:1910-1945: brightfield/ (as read), alive/ and dead/ (soft vote), mod_position/ (3-channel circles)."""
+    out = _vote_out_dirs(main_output_path, ("brightfield", "alive", "dead", "mod_position"))
+
+    def per_image(name, img, m):
+        return [(os.path.join(out["brightfield"], name), img), (os.path.join(out["alive"], name), m[0]),
+                (os.path.join(out["dead"], name), m[1]), (os.path.join(out["mod_position"], name), _hela_vote_positions(m[2], 8, 3))]
+    _run_vote_writer(models, bf_images_path, c, True, True, 0.5, False, per_image)
 
 
 _HELA_GT_COUNTS = {}      # id(position-mask tensor of a cached decoded set) -> (weak reference to it, [(alive, dead)] ground-truth cell counts)

@@ -11,7 +11,12 @@ generation (Noisy Student).
 approach="aug_IM_plus" is AIM+ (ISIC_2018/13_ISIC_2018_aug_IM+.py:44-116, HeLa/13_HeLa_aug_IM+.py, Cityscapes/13_Cityscapes_aug_IM+.py,
 SUIM/14_SUIM_aug_IM+.py): IM+ that starts from the augmented-subset baseline (`*_subset_aug_{runid}_topK_j.h5`,
 subset_driver.run(..., aug=True)), keeps the un-augmented IM pairs beside their augmented copies and adds the AUGMENTED
-labelled set (TRAIN_LABELED_AUG) instead of the plain one; the multi-class scripts honour FILTER_INCONSISTENT_CLASS_PRED."""
+labelled set (TRAIN_LABELED_AUG) instead of the plain one; the multi-class scripts honour FILTER_INCONSISTENT_CLASS_PRED.
+
+approach="model_ensemble" is the model-ensemble baseline (ISIC_2018/06_ISIC_2018_model_ensemble.py, HeLa/06_HeLa_model_ensemble.py,
+SUIM/07_SUIM_model_ensemble.py, Cityscapes/06_Cityscapes_model_ensemble.py): the IM loop with the ensemble's vote in place of the
+IM writer (create_pseudo_labels_model_ensemble_*: no im/ directory, no blocking, no mean_im_size CSV), model names without the
+erode / dilate / blocking suffix, and HeLa candidates ranked by mean_cell_count_error_test, ascending (HeLa/06_HeLa_model_ensemble.py:120)."""
 import csv
 import os
 import shutil
@@ -223,6 +228,8 @@ def run(dataset, approach="IM", parallel_candidates=None):
         BI, BO = S["BLOCK_INPUT"].lower() == "true", S["BLOCK_OUTPUT"].lower() == "true"
     filt = S.get("FILTER_INCONSISTENT_CLASS_PRED", "false").lower() == "true"
     aim = approach == "aug_IM_plus"
+    ens = approach == "model_ensemble"
+    rank_idx, rank_desc = (6, False) if (ens and ds["kind"] == "hela") else (ds["rank"], True)
     plus = IM_PLUS[dataset] if approach in ("IM_plus", "aug_IM_plus") else None
     if plus:    # the IM+ scripts parse the blocking flags properly for every dataset (ISIC_2018/11_...IM+.py:38-39)
         BI, BO = S["BLOCK_INPUT"].lower() == "true", S["BLOCK_OUTPUT"].lower() == "true"
@@ -238,8 +245,8 @@ def run(dataset, approach="IM", parallel_candidates=None):
     for runid in _ints("IM_RUNIDS", [1, 2, 3]):
         for n in _ints("IM_NS", [2, 3, 4]):
             for gen in _ints("IM_GENS", [0, 1, 2, 3, 4]):
-                name_of = lambda g: f"{tag}_{approach}_{runid}_n{n}_gen{g}_e{EK}_d{DK}_bi_{BI}_bo_{BO}" + \
-                    ("_filtered" if (filt and ds["kind"] == "multi") else "")
+                name_of = lambda g: f"{tag}_{approach}_{runid}_n{n}_gen{g}" + ("" if ens else f"_e{EK}_d{DK}_bi_{BI}_bo_{BO}") + \
+                    ("_filtered" if (filt and ds["kind"] == "multi" and not ens) else "")
                 modelname = name_of(gen)
                 out = {k: os.path.join(base, f"{k}_predictions", approach, *(["temp"] if plus else []), modelname)
                        for k in ("val", "test", "train_unlabeled")}
@@ -252,7 +259,14 @@ def run(dataset, approach="IM", parallel_candidates=None):
 
                 means = []
                 for split, key in (("VAL", "val"), ("TEST", "test"), ("TRAIN_UNLABELED", "train_unlabeled")):
-                    if ds["kind"] == "isic":
+                    if ens and ds["kind"] == "isic":
+                        F.create_pseudo_labels_model_ensemble_ISIC_2018(best_models, P(f"{split}_IMAGES_DIR"), out[key], H, W, C, True)
+                    elif ens and ds["kind"] == "multi":
+                        F.create_pseudo_labels_model_ensemble_multiclass(best_models, P(f"{split}_IMAGES_DIR"), out[key], H, W, C, True)
+                    elif ens:
+                        F.create_pseudo_labels_model_ensemble_hela(best_models, os.path.join(P(f"{split}_DIR"), "brightfield"), out[key],
+                                                                   H, W, C)
+                    elif ds["kind"] == "isic":
                         means.append(F.create_pseudo_labels_im_ISIC_2018(best_models, H, W, C, P(f"{split}_IMAGES_DIR"), out[key],
                                                                          True, EK, DK, BI, BO, True))
                     elif ds["kind"] == "multi":
@@ -261,7 +275,7 @@ def run(dataset, approach="IM", parallel_candidates=None):
                     else:
                         means.append(F.create_pseudo_labels_im_hela(best_models, H, W, C, os.path.join(P(f"{split}_DIR"), "brightfield"),
                                                                     out[key], EK, DK, BI, BO))
-                tick("pseudo-labels (val, test, unlabeled): ensemble inference + IM + PNG I/O")
+                tick("pseudo-labels (val, test, unlabeled): ensemble inference + " + ("vote" if ens else "IM") + " + PNG I/O")
                 unl = out["train_unlabeled"]
                 if plus:     # augmented copies only (copy_org False) form the training set
                     src, unl = unl, os.path.join(base, "train_unlabeled_predictions", approach, modelname)
@@ -316,7 +330,7 @@ def run(dataset, approach="IM", parallel_candidates=None):
                 rows = train_candidates(_ints("IM_CANDIDATES", [0, 1, 2, 3, 4]), train_candidate, world, tick, parallel_candidates)
 
                 if rank == 0:
-                    top = sorted(rows, key=lambda r: r[ds["rank"]], reverse=True)[:top_k]
+                    top = sorted(rows, key=lambda r: r[rank_idx], reverse=rank_desc)[:top_k]
                     print(top)
                     for i, row in enumerate(top, start=1):
                         os.rename(os.path.join(model_dir, f"{row[0]}.h5"), os.path.join(model_dir, f"{row[0][:-2]}_topK_{i}.h5"))
@@ -331,9 +345,10 @@ def run(dataset, approach="IM", parallel_candidates=None):
                         with open(os.path.join(csv_dir, f"results_{modelname}.meta.json"), "w", encoding="utf-8") as f:
                             json.dump({"data_parallel_ranks": world, "dp_mode": dp_mode(), "batch_per_rank": batch, "bn_momentum_rule": rule,
                                        "bn_momentum": round(mom, 6), "env": "IMK_DP_BN_MOMENTUM"}, f)
-                    with open(os.path.join(csv_dir, f"mean_im_size_{modelname}.csv"), "w", encoding="utf-8", newline="") as f:
-                        wr = csv.writer(f, delimiter=";")
-                        wr.writerow(["val_mean_im_size", "test_mean_im_size", "unlabeled_mean_im_size"])
-                        wr.writerow(means)
+                    if not ens:     # the model-ensemble scripts write no IM sizes
+                        with open(os.path.join(csv_dir, f"mean_im_size_{modelname}.csv"), "w", encoding="utf-8", newline="") as f:
+                            wr = csv.writer(f, delimiter=";")
+                            wr.writerow(["val_mean_im_size", "test_mean_im_size", "unlabeled_mean_im_size"])
+                            wr.writerow(means)
                 if torch.distributed.is_initialized():
                     torch.distributed.barrier()
