@@ -252,23 +252,16 @@ __global__ __launch_bounds__(256, SMALL ? BWD1_SMALL_WGS : 2) void bwd1x1_kernel
     IMK_STAMP_END(1);
 }
 
-bool bwd1_env_on() {
-    static const bool on = []() { const char *e = getenv("IMK_BWD1X1"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
 }  // namespace
 
 int imk_bwd1x1_rows(long long n_pix, int cs_in, int cs_out) {
     const long long n_tiles = (n_pix + 127) / 128;
-    static const int cap_small = []() { const char *e = getenv("IMK_BWD1X1_ROWS"); return e ? atoi(e) : 256 * BWD1_SMALL_WGS; }();
-    const int cap = (cs_in <= 32 && cs_out <= 32) ? cap_small : 512;   // 3 workgroups per compute unit in the <= 32-channel form (4 fit and measured slower: more partial rows), 2 above
+    const int cap = (cs_in <= 32 && cs_out <= 32) ? 256 * BWD1_SMALL_WGS : 512;   // 3 workgroups per compute unit in the <= 32-channel form (4 fit and measured slower: more partial rows), 2 above
     return (int)(n_tiles < cap ? n_tiles : cap);
 }
 
 // Conv1x1 with 17-64 (padded) channels on both sides, reading a plain fp16 tensor (the ReLU mask of its dgrad) or upsample + add
 bool imk_bwd1x1_ok(int lmode, int cs_in, int cs_out, bool masked) {
-    if (!bwd1_env_on()) return false;
     if (cs_in < 24 || cs_in > 64 || cs_out < 24 || cs_out > 64) return false;
     if (lmode == LM_RAW) return masked;
     return lmode == LM_UPADD && !masked;

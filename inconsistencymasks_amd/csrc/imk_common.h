@@ -21,8 +21,6 @@ struct ImkStopRing {
     int n, cur;
     hipStream_t stream;          // the main stream of the pass
     hipEvent_t last;             // event bound to its most recent kernel
-    hipStream_t side = nullptr;  // (optional) the pass's one side stream: its last kernel's event serves the join at the end
-    hipEvent_t side_last = nullptr;
 };
 inline thread_local ImkStopRing *imk_tls_stop_ring = nullptr;
 // Measurement (imk_prof_totals_enable on the context bound to this thread): every launch is counted under the kernel's own name as
@@ -44,12 +42,12 @@ inline void imk_klaunch(void (*kern)(KA...), dim3 grid, dim3 block, size_t lds, 
     static_assert(sizeof...(KA) == sizeof...(A), "kernel argument count");
     if (imk_tls_totals_on) imk_prof_note_launch(reinterpret_cast<const void *>(kern), stream);
     ImkStopRing *r = imk_tls_stop_ring;
-    if (r && (r->stream == stream || (r->side && r->side == stream))) {
+    if (r && r->stream == stream) {
         hipEvent_t e = r->ev[r->cur];
         r->cur = (r->cur + 1) % r->n;
         const bool ok = imk_klaunch_ext(kern, grid, block, lds, stream, e, std::index_sequence_for<KA...>{}, std::forward<A>(args)...) == hipSuccess;
         // (on failure the error stays pending for IMK_LAUNCH_CHECK and forks / joins fall back to recorded events)
-        (r->stream == stream ? r->last : r->side_last) = ok ? e : nullptr;
+        r->last = ok ? e : nullptr;
         return;
     }
     kern<<<grid, block, lds, stream>>>(static_cast<KA>(args)...);

@@ -23,10 +23,8 @@
 #include "imk_elem.h"
 
 #include "imk_stage.h"
+#include "imk_switches.h"
 
-#ifndef IMK_ABL
-#define IMK_ABL 0
-#endif
 #ifndef IMK_INF_WAVES
 #define IMK_INF_WAVES 4      // waves per SIMD the 8-channel inference instantiations of conv_pipe_kernel are compiled for (probe builds: 5)
 #endif
@@ -622,11 +620,7 @@ __global__ __launch_bounds__(256, (DYN && NC8 == 1) ? IMK_INF_WAVES : 1) void co
         valid = 0;
 #pragma unroll
         for (int k = 0; k < MAX_ITEMS; ++k) {
-#if IMK_ABL & 1
-            const bool in_img = psrc_load<LM, CSB>(src, 1, 1, 0, W, raw[k]) || true;      // every lane the same (cached) address
-#else
             const bool in_img = psrc_load<LM, CSB>(src, it_py[k], it_px[k], it_c8[k], W, raw[k]);
-#endif
             valid |= ((it_lds[k] >= 0 && in_img) ? 1u : 0u) << k;
         }
         if constexpr (WG == 1 || WG == 2) {      // thread t <-> pixel t of the (full) tile
@@ -697,13 +691,7 @@ __global__ __launch_bounds__(256, (DYN && NC8 == 1) ? IMK_INF_WAVES : 1) void co
 #pragma unroll
             for (int k = 0; k < MAX_ITEMS; ++k) {
                 if (it_lds[k] >= 0) {
-#if IMK_ABL & 4
-                    f16x8 v;
-                    if constexpr (LM == LM_U8 || LM == LM_STEM) v = raw_transform<LM>(raw[k], s_aff, cs_in, it_c8[k], a.x.cin, a.x.u8_div, a.x.u8_c);
-                    else v = raw[k].v[0];
-#else
                     f16x8 v = raw_transform<LM>(raw[k], s_aff, cs_in, it_c8[k], a.x.cin, a.x.u8_div, a.x.u8_c);
-#endif
                     if (!(valid & (1u << k))) v = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
                     *reinterpret_cast<f16x8 *>(s_stage + it_lds[k]) = v;
                 }
@@ -786,7 +774,7 @@ __global__ __launch_bounds__(256, (DYN && NC8 == 1) ? IMK_INF_WAVES : 1) void co
         }
         issue(tn);                                // in flight during the MFMAs, the epilogue and its stores
         if constexpr (DYN) tk_new = imk_take_ticket(tk_head, tk_lane);     // the tile after next: its latency runs under this tile
-        if constexpr (PRE && !(IMK_ABL & 8)) {
+        if constexpr (PRE) {
             // rows / columns of the halo tile that lie inside the image (the 3x3 pads its INPUT with zeros, not the 1x1's)
             const int oy = tc.ty0 - halo, ox = tc.tx0 - halo;
             const int lo_y = oy < 0 ? -oy : 0, hi_y = min(HT - 1, H - 1 - oy), lo_x = ox < 0 ? -ox : 0, hi_x = min(WT - 1, W - 1 - ox);
@@ -810,16 +798,6 @@ __global__ __launch_bounds__(256, (DYN && NC8 == 1) ? IMK_INF_WAVES : 1) void co
                 const f16x4 w = __builtin_bit_cast(f16x4, uint2{wd[0], wd[1]});
                 if (pre_cb < NC8 * 8)
                     *reinterpret_cast<f16x4 *>(s_tile + (pre_pix[j] * PS + (pre_cb >> 3)) * 16 + (pre_cb & 7) * 2) = w;
-#ifdef IMK_PRE_DEBUG      // probe builds (tests/gpu_probe/pre_dump.py): the first stage's values of the tile's own pixels, for a per-pixel diff
-                if (a.out && pre_cb < NC8 * 8 && py >= 1 && py <= 16 && px >= 1 && px <= 16 && inside) {
-                    const size_t gp = ((size_t)(tc.b * H + tc.ty0 + py - 1) * W + tc.tx0 + px - 1) * (NC8 * 8) + pre_cb;
-                    f16x4 zv;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) zv[r] = (f16)fmaxf(pa[r] + pb[r], 0.f);
-                    *reinterpret_cast<f16x4 *>(const_cast<f16 *>(a.mask) + gp) = zv;      // pre-BatchNorm (what the 1x1's own launch stores)
-                    *reinterpret_cast<f16x4 *>(a.out + gp) = w;                            // after the BatchNorm (the 3x3's input)
-                }
-#endif
             }
             __syncthreads();      // the 3x3's input tile is complete
         }
@@ -886,7 +864,7 @@ __global__ __launch_bounds__(256, (DYN && NC8 == 1) ? IMK_INF_WAVES : 1) void co
 #pragma unroll
         for (int p = 0; p < P; ++p) acc[p] = f32x4{0, 0, 0, 0};
 #pragma unroll
-        for (int s = 0; s < ((IMK_ABL & 16) ? 1 : MAX_NS); ++s) {
+        for (int s = 0; s < MAX_NS; ++s) {
             if (s < ns) {
 #pragma unroll
                 for (int p = 0; p < P; ++p) {
@@ -905,7 +883,7 @@ __global__ __launch_bounds__(256, (DYN && NC8 == 1) ? IMK_INF_WAVES : 1) void co
                 const f16x8 bf2 = {hv[0], hv[1], hv[2], hv[3], 0, 0, 0, 0};
                 const f32x4 a2 = __builtin_amdgcn_mfma_f32_16x16x32_f16(af2, bf2, f32x4{0, 0, 0, 0}, 0, 0, 0);
                 const f16x4 v = imk_bias_relu4(a2, bias2);
-                if ((FULL || inb[p]) && lane_out && (!(IMK_ABL & 2) || a.H < 0)) {
+                if ((FULL || inb[p]) && lane_out) {
                     *reinterpret_cast<f16x4 *>(const_cast<char *>(b_o2) + o2[p]) = v;
                     if (want_stats)
 #pragma unroll
@@ -1837,18 +1815,14 @@ int imk_launch_pack_jobs(const ImkPackJobs &jobs, hipStream_t stream) {
     // the kernel sits at the very end of the step's dependent chain, and a slot is a chain of index divisions and one load
     // Round 5: wider nets get more blocks (EvalNet alpha 2 / Cityscapes alpha 2: 2.4 M slots in the widest layer = 144 per thread on
     // 64 blocks, 44 us per launch): about 8 slots per thread of the widest job, 64 ... 1024 blocks per job (a block whose job has
-    // fewer slots leaves at once).  IMK_PACK_BLOCKS fixes the count.
-    static const int bpj_env = []() { const char *e = getenv("IMK_PACK_BLOCKS"); return e ? atoi(e) : 0; }();
-    int bpj = bpj_env;
-    if (bpj <= 0) {
-        long long widest = 0;
-        for (int i = 0; i < jobs.n; ++i) {
-            const long long slots = (long long)jobs.j[i].ksize * jobs.j[i].ksize * ((jobs.j[i].cin + 15) & ~15) * ((jobs.j[i].cout + 15) & ~15);
-            widest = slots > widest ? slots : widest;
-        }
-        bpj = (int)((widest + 2047) / 2048);
-        bpj = bpj < 64 ? 64 : (bpj > 1024 ? 1024 : bpj);
+    // fewer slots leaves at once).
+    long long widest = 0;
+    for (int i = 0; i < jobs.n; ++i) {
+        const long long slots = (long long)jobs.j[i].ksize * jobs.j[i].ksize * ((jobs.j[i].cin + 15) & ~15) * ((jobs.j[i].cout + 15) & ~15);
+        widest = slots > widest ? slots : widest;
     }
+    int bpj = (int)((widest + 2047) / 2048);
+    bpj = bpj < 64 ? 64 : (bpj > 1024 ? 1024 : bpj);
     imk_klaunch(pack_conv_batched_kernel, dim3(dim3(bpj, jobs.n)), dim3(256), 0, stream, jobs);
     IMK_LAUNCH_CHECK();
     return IMK_OK;
@@ -2142,15 +2116,13 @@ static int launch_conv_mfma(const ImkConvArgs &a, hipStream_t stream) {
 static bool pipe_fits(const ImkConvArgs &a) { return (long long)a.H * a.W < imk_conv_max_pixels() && a.W < (1 << 16); }
 
 
-static bool dyn_walk_on() {
-    static const bool on = []() { const char *e = getenv("IMK_DYN_WALK"); return !(e && e[0] == '0'); }();
-    return on;
-}
+// resident workgroups per CU a pipelined launch is sized for, at most (fewer where the instantiation's occupancy is lower)
+constexpr int PIPE_BLOCKS_PER_CU = 8;
 
 template <int LM, int NC8, int CHAIN, bool PAIR, int EPI, bool DYSTAT, bool FULL, int WG = 0, int PRE = 0, bool DYN = false>
 static int launch_conv_pipe_k(const ImkConvArgs &a, hipStream_t stream) {
     if constexpr (!DYN && EPI == EP_RELU && !DYSTAT && WG == 0) {      // inference launches with tile counters: the dynamic walk
-        if (a.sched && !a.stats_partial && dyn_walk_on() && a.B * imk_cdiv(a.H, 16) * imk_cdiv(a.W, TW) >= 2048)
+        if (a.sched && !a.stats_partial && a.B * imk_cdiv(a.H, 16) * imk_cdiv(a.W, TW) >= 2048)
             return launch_conv_pipe_k<LM, NC8, CHAIN, PAIR, EPI, DYSTAT, FULL, WG, PRE, true>(a, stream);
     }
     if (a.x.cs_in != (PRE ? PRE : NC8) * 8) return IMK_EINVAL;      // the kernel takes the input's channel stride from its template arguments
@@ -2160,8 +2132,7 @@ static int launch_conv_pipe_k(const ImkConvArgs &a, hipStream_t stream) {
     if (blocks_per_cu == 0) {
         int nb = 0;
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, lds) != hipSuccess || nb < 1) nb = 4;
-        static const int cap = []() { const char *e = getenv("IMK_PIPE_BLOCKS_PER_CU"); return e ? atoi(e) : 8; }();
-        blocks_per_cu = nb > cap ? cap : nb;
+        blocks_per_cu = nb > PIPE_BLOCKS_PER_CU ? PIPE_BLOCKS_PER_CU : nb;
     }
     const int tiles_x = imk_cdiv(a.W, TW), tiles_y = imk_cdiv(a.H, 16);
     const int n_tiles = a.B * tiles_x * tiles_y;
@@ -2182,9 +2153,7 @@ template <int NC8, bool PAIR, bool FULL>
 static int launch_conv_pipe_v(const ImkConvArgs &a, hipStream_t stream) {
     if (a.pre_wpk) {        // 1x1 first stage + 3x3 + chained 1x1 (inference); instantiated for the pair layout (imk_conv_can_prestage)
         if constexpr (PAIR && NC8 == 1) {
-#ifndef IMK_PRE_DEBUG     // (the probe build passes dump tensors in a.out / a.mask)
             if (a.out) return IMK_EUNSUPPORTED;
-#endif
             if (a.epi != EP_RELU || !a.wpk2 || a.x.lmode != LM_UPADD || a.x.cs_in != 8) return IMK_EUNSUPPORTED;
             return launch_conv_pipe_k<LM_UPADD, 1, 2, true, EP_RELU, false, FULL, 0, 1>(a, stream);
         } else {
@@ -2315,8 +2284,7 @@ static int launch_conv_wide_v(const ImkConvArgs &a, hipStream_t stream) {
 
 // 17-32 channels on at least one side, at most 32 on both: the wide persistent kernel (see conv_wide_kernel)
 static bool conv_wide_ok(const ImkConvArgs &a) {
-    static const bool off = []() { const char *e = getenv("IMK_CONV_WIDE"); return e && e[0] == '0'; }();
-    if (off || a.wpk2 || a.x.cs_in > 32 || a.cout > 32 || !pipe_fits(a)) return false;
+    if (!imk_switches().conv_wide || a.wpk2 || a.x.cs_in > 32 || a.cout > 32 || !pipe_fits(a)) return false;
     if (a.x.lmode == LM_POOL || a.x.lmode == LM_STEM) return false;
     if (a.x.lmode == LM_U8 && a.x.cin > 4) return false;
     return true;
@@ -2324,10 +2292,9 @@ static bool conv_wide_ok(const ImkConvArgs &a) {
 
 // Conv3x3+ReLU -> Conv1x1+ReLU in one launch of the wide kernel (inference: the intermediate is not stored, no statistics)
 static bool conv_wide_chain_ok(const ImkConvArgs &a) {
-    static const bool off = []() { const char *e = getenv("IMK_WIDE_CHAIN"); return e && e[0] == '0'; }();
-    static const bool train_off = []() { const char *e = getenv("IMK_WIDE_CHAIN_TRAIN"); return e && e[0] == '0'; }();
-    if (off || !a.wpk2 || a.epi != EP_RELU || a.ksize != 3) return false;
-    if ((a.out || a.stats_partial) && (train_off || a.cout2 > a.cout)) return false;   // training: intermediate stored, statistics of the 1x1's output
+    const ImkSwitches &sw = imk_switches();
+    if (!sw.wide_chain || !a.wpk2 || a.epi != EP_RELU || a.ksize != 3) return false;
+    if ((a.out || a.stats_partial) && (!sw.wide_chain_train || a.cout2 > a.cout)) return false;   // training: intermediate stored, statistics of the 1x1's output
     if (a.x.cs_in < 16 || a.x.cs_in > 32 || a.cout > 32 || a.cout2 > 32 || (a.x.cs_in <= 16 && a.cout <= 16)) return false;
     if (a.x.lmode != LM_AFFINE) return false;     // (the pooled-input form, alpha 1's second encoder block, gains nothing: 1.170 vs 1.166 ms)
     ImkConvArgs plain = a;
@@ -2366,36 +2333,34 @@ static int launch_conv_wide_any(const ImkConvArgs &a, hipStream_t stream) {
 #undef IMK_WIDE_SEL
 }
 
-static bool pipe_enabled() {
-    static const bool on = []() { const char *e = getenv("IMK_CONV_PIPE"); return !(e && e[0] == '0'); }();
-    return on;
-}
-static bool pair_enabled() {
-    static const bool on = []() { const char *e = getenv("IMK_CONV_PAIR"); return !(e && e[0] == '0'); }();
-    return on && pipe_enabled();
+// The pipelined kernel (conv_pipe_kernel: at most 16 channels on both sides) and its fragment layout -- the pair layout, two
+// 8-channel output tiles per fragment, wherever the conv has at most 8 output channels (the weights' side: imk_conv_pair_layout).
+// imk_launch_conv and every planner below take their choice from here.
+struct PipeChoice { bool ok, pair; };
+static PipeChoice pipe_choice(const ImkConvArgs &a) {
+    const bool ok = pipe_fits(a) && a.x.cs_in <= 16 && a.cout <= 16 && (a.x.lmode != LM_U8 || a.x.cin <= 4) &&
+                    (!a.pre_wpk || imk_pad8(a.pre_cout) <= 16);
+    return {ok, ok && a.cout <= 8};
 }
 
 bool imk_conv_pair_layout(int k_in, int m_out, bool u8_input) {
-    return pair_enabled() && imk_pad8(k_in) <= 16 && m_out <= 8 && (!u8_input || k_in <= 4);
+    return imk_pad8(k_in) <= 16 && m_out <= 8 && (!u8_input || k_in <= 4);
 }
 
 bool imk_conv_stem_fusable(int u8_c, int ch0, int cout_next) {
-    static const bool off = []() { const char *e = getenv("IMK_STEM_FUSE"); return e && e[0] == '0'; }();
-    return !off && pipe_enabled() && u8_c <= 4 && ch0 <= 16 && cout_next <= 16;
+    return u8_c <= 4 && ch0 <= 16 && cout_next <= 16;
 }
 
 bool imk_conv_can_chain(const ImkConvArgs &a, int cout2) {
-    static const bool off = []() { const char *e = getenv("IMK_CONV_CHAIN"); return e && e[0] == '0'; }();
-    if (off || !pipe_enabled() || !pipe_fits(a)) return false;
-    if (pair_enabled() && a.cout <= 8 && cout2 > 8) return false;   // the two stages must use the same fragment layout
-    return a.epi == EP_RELU && a.x.cs_in <= 16 && a.cout <= 16 && cout2 <= 16 && (a.x.lmode != LM_U8 || a.x.cin <= 4);
+    const PipeChoice p = pipe_choice(a);
+    if (!p.ok || (p.pair && cout2 > 8)) return false;   // the two stages must use the same fragment layout
+    return a.epi == EP_RELU && cout2 <= 16;
 }
 
 // conv_pipe_kernel<..., PRE>: `main` is a chained 3x3 launch of the shallow kernel without a stored intermediate (inference);
 // the 1x1 in front of it reads a uint8 image or upsample + skip with at most 16 channels and uses the same weight layout.
 bool imk_conv_can_prestage(const ImkConvArgs &a, int lm_pre, int cin_pre, int cout_pre) {
-    static const bool off = []() { const char *e = getenv("IMK_CONV_PRESTAGE"); return e && e[0] == '0'; }();
-    if (off || !pipe_enabled() || !pipe_fits(a)) return false;
+    if (!imk_switches().conv_prestage || !pipe_fits(a)) return false;
     if (a.epi != EP_RELU || a.ksize != 3 || !a.wpk2 || a.out) return false;
     // Measured (inference call of 128 images, ms without / with): ISIC (8 channels, pair layout) 0.538 / 0.503 -- the decoder's
     // full- and half-resolution blocks 117.9 -> 104.5 us and 61.0 -> 53.8 us; SUIM (16 channels, plain layout: 170 VGPRs, two
@@ -2414,76 +2379,56 @@ bool imk_conv_can_prestage(const ImkConvArgs &a, int lm_pre, int cin_pre, int co
 // chain when the intermediate is not stored or the launch is small (EvalNet's full-resolution towers in training: 2.87 ms
 // per step as two conv_wide launches, 2.94 chained).  IMK_CONV_CHAIN_TILE = 0 off, 2 always.
 bool imk_conv_can_chain_tile(const ImkConvArgs &a, int cout2, bool store_mid) {
-    static const int mode = []() { const char *e = getenv("IMK_CONV_CHAIN_TILE"); return e ? atoi(e) : 1; }();
-    if (mode == 0) return false;
+    const ImkSwitches &sw = imk_switches();
+    if (sw.conv_chain_tile == 0) return false;
+    ImkConvArgs plain = a;
+    plain.wpk2 = nullptr;
+    // the GEMM-class chain (imk_conv_gemm_chain_ok, before wpk2 is set), in training as well
+    if (a.epi == EP_RELU && a.ksize == 3 && (a.x.lmode == LM_POOL || a.x.lmode == LM_AFFINE) && a.cout <= 128 &&
+        cout2 <= 128 && imk_pad8(cout2) <= (a.cout > 64 ? 128 : 64) && sw.gemm_chain && imk_conv_gemm_ok(plain))
+        return true;
     // Where the GEMM-class kernel would take the 3x3 (imk_gemm.hip): IMK_GEMM_OVER_CHAIN = 0 chain anyway, 1 two launches when
     // the intermediate is stored anyway (training), 2 always two launches
-    static const int over = []() { const char *e = getenv("IMK_GEMM_OVER_CHAIN"); return e ? atoi(e) : 1; }();
-    if (a.epi == EP_RELU && a.ksize == 3 && (a.x.lmode == LM_POOL || a.x.lmode == LM_AFFINE) && a.cout <= 128 &&
-        cout2 <= 128 && imk_pad8(cout2) <= (a.cout > 64 ? 128 : 64)) {     // the GEMM-class chain (imk_conv_gemm_chain_ok, before wpk2 is set)
-        static const bool gc_off = []() { const char *e = getenv("IMK_GEMM_CHAIN"); return e && e[0] == '0'; }();
-        // training (store_mid): IMK_GEMM_CHAIN_TRAIN = 0 off, 2 only where the two convs have the same width (encoder blocks: the
-        // chain's statistics rows are then bit for bit those of the 1x1's own launch), 1 (default) everywhere
-        static const int gct = []() { const char *e = getenv("IMK_GEMM_CHAIN_TRAIN"); return e ? atoi(e) : 1; }();
-        ImkConvArgs plain = a;
-        plain.wpk2 = nullptr;
-        const bool train_ok = gct == 1 || (gct == 2 && imk_pad8(cout2) == a.cs_out);
-        if (!gc_off && (!store_mid || train_ok) && imk_conv_gemm_ok(plain)) return true;
-    }
-    if (over == 2 || (over == 1 && store_mid)) {
-        ImkConvArgs plain = a;
-        plain.wpk2 = nullptr;
-        if (imk_conv_gemm_ok(plain)) return false;
-    }
-    const bool pipe_ok = pipe_enabled() && pipe_fits(a) && a.x.cs_in <= 16 && a.cout <= 16;
-    if (pipe_ok || a.epi != EP_RELU || a.ksize != 3 || a.cout > 64 || cout2 > 64) return false;
+    if ((sw.gemm_over_chain == 2 || (sw.gemm_over_chain == 1 && store_mid)) && imk_conv_gemm_ok(plain)) return false;
+    if (pipe_choice(a).ok || a.epi != EP_RELU || a.ksize != 3 || a.cout > 64 || cout2 > 64) return false;
     if (a.x.lmode != LM_POOL && a.x.lmode != LM_AFFINE) return false;
     const bool wide = a.x.cs_in <= 32 && a.cout <= 32 && a.x.lmode != LM_POOL;     // conv_wide_kernel's layers
     // (large launches of these layers in training: two conv_wide launches beat the per-tile chain; the persistent kernel's own
     //  chain -- conv_wide_kernel<..., CHAIN2>, round 3 -- beats both where it applies)
-    static const bool wct_off = []() { const char *e = getenv("IMK_WIDE_CHAIN_TRAIN"); return e && e[0] == '0'; }();
-    const bool wide_chain = !wct_off && wide && a.x.lmode == LM_AFFINE && a.x.cs_in >= 16 && cout2 <= a.cout && pipe_fits(a);
-    if (mode == 1 && wide && store_mid && !wide_chain && (long long)a.B * imk_cdiv(a.H, 16) * imk_cdiv(a.W, TW) > 2048) return false;
+    const bool wide_chain = sw.wide_chain_train && wide && a.x.lmode == LM_AFFINE && a.x.cs_in >= 16 && cout2 <= a.cout && pipe_fits(a);
+    if (sw.conv_chain_tile == 1 && wide && store_mid && !wide_chain && (long long)a.B * imk_cdiv(a.H, 16) * imk_cdiv(a.W, TW) > 2048)
+        return false;
     const int mt1 = (a.cout + 15) / 16, mt2 = (cout2 + 15) / 16, mt = (mt1 <= 2 && mt2 <= 2) ? 2 : 4;
     return mt1 <= mt && mt2 <= mt && conv_tile_h(a.x.cs_in, 3) == 16;
 }
 
-// Can this dgrad launch also produce the weight gradient of its conv (ImkConvArgs::wg_partial)?  Mirrors the choices of
-// imk_launch_conv / launch_conv_pipe_any: pipelined kernel, full tiles, every lane owning real channels.
+// Can this dgrad launch also produce the weight gradient of its conv (ImkConvArgs::wg_partial)?  The pipelined kernel
+// (pipe_choice), full tiles, every lane owning real channels.
 bool imk_conv_can_fuse_wgrad(const ImkConvArgs &a) {
-    static const bool off = []() { const char *e = getenv("IMK_FUSE_WGRAD"); return e && e[0] == '0'; }();
-    if (off || !pipe_enabled() || !pipe_fits(a)) return false;
-    if (a.wpk2) return false;
+    const PipeChoice p = pipe_choice(a);
+    if (!p.ok || a.wpk2) return false;
     const bool form1 = a.ksize == 1 && a.x.lmode == LM_BNBWD && a.epi == EP_MASK && a.mask && !(a.dystat_z && a.stats_partial);
     const bool form2 = a.x.lmode == LM_RAW && a.epi == EP_PLAIN && a.dystat_z && a.stats_partial;     // 1x1 and 3x3
     // The 3x3 form doubles the launch's matrix and LDS work (20 MFMAs + 40 transposed reads per wave and tile on top of the dgrad's 20):
     // at ISIC the half-resolution 16-channel launch takes 42 us fused against ~20 us for the plain dgrad.  Round 5 measured the
-    // alternatives on one box against round 4's library (IMK_FUSE_WGRAD_C3: 0 = never fuse the 3x3 form, 8 = pair layout only, unset =
-    // wherever it applies): ISIC / SUIM / HeLa steps within +-0.5 % of each other under every rule -- what the chain gains, the fork and
-    // the weight-gradient launch beside it give back (profiles/r05_notes.md).  The default stays "wherever it applies".
-    static const int c3_mode = []() { const char *e = getenv("IMK_FUSE_WGRAD_C3"); return e ? atoi(e) : -1; }();
+    // alternatives on one box against round 4's library (never fuse the 3x3 form, pair layout only, wherever it applies): ISIC /
+    // SUIM / HeLa steps within +-0.5 % of each other under every rule -- what the chain gains, the fork and the weight-gradient
+    // launch beside it give back (profiles/r05_notes.md).  The rule is "wherever it applies"; the switch that chose is removed.
     if (!form1 && !form2) return false;
-    if (a.ksize == 3 && (c3_mode == 0 || (c3_mode == 8 && a.cout > 8))) return false;
-    if (a.x.cs_in > 16 || a.cout > 16) return false;
-    const bool pair = pair_enabled() && a.cout <= 8;
-    const bool all_ch = pair || a.cs_out == 16;
-    return (a.H % 16 == 0) && (a.W % TW == 0) && all_ch && (pair ? a.cs_out == 8 : true);
+    const bool all_ch = p.pair ? a.cs_out == 8 : a.cs_out == 16;
+    return (a.H % 16 == 0) && (a.W % TW == 0) && all_ch;
 }
 int imk_conv_fused_wgrad_rows_max() { return 256 * 8; }
 
-// Can this 1x1 dgrad launch also emit the 2x2 sums of its output (ImkConvArgs::sum2_out)?  The pipelined kernel, full tiles, every
-// lane owning real channels -- what launch_conv_pipe_any would pick for it.
+// Can this 1x1 dgrad launch also emit the 2x2 sums of its output (ImkConvArgs::sum2_out)?  The pipelined kernel (pipe_choice),
+// full tiles, every lane owning real channels.
 bool imk_conv_can_sum2(const ImkConvArgs &a) {
-    static const bool off = []() { const char *e = getenv("IMK_FUSE_SUM2"); return e && e[0] == '0'; }();
-    if (off || !pipe_enabled() || !pipe_fits(a) || a.wpk2 || a.wg_partial) return false;
+    const PipeChoice p = pipe_choice(a);
+    if (!p.ok || a.wpk2 || a.wg_partial) return false;
     if (a.ksize != 1 || a.x.lmode != LM_BNBWD || a.epi != EP_PLAIN || (a.dystat_z && a.stats_partial)) return false;
-    if (a.x.cs_in > 16 || a.cout > 16) return false;
-    const bool pair = pair_enabled() && a.cout <= 8;
-    const bool all_ch = pair ? a.cs_out == 8 : a.cs_out == 16;
+    const bool all_ch = p.pair ? a.cs_out == 8 : a.cs_out == 16;
     return (a.H % 16 == 0) && (a.W % TW == 0) && all_ch;
 }
-
-static bool g_use_pipe = true;   // IMK_CONV_PIPE=0 in the environment falls back to the per-tile kernel (A/B runs)
 
 int imk_launch_conv(const ImkConvArgs &a_in, hipStream_t stream) {
     ImkConvArgs a = a_in;
@@ -2492,22 +2437,19 @@ int imk_launch_conv(const ImkConvArgs &a_in, hipStream_t stream) {
     IMK_CHECK_ARG(a.x.cs_in % 8 == 0 && a.cs_out % 8 == 0 && a.x.cs_in >= a.x.cin && a.cs_out >= a.cout);
     IMK_CHECK_ARG(a.x.lmode != LM_U8 || (a.x.cs_in == 8 && a.x.cin <= 8));
     if (a.x.cs_in > 512) return IMK_EUNSUPPORTED;
-    static const bool env_checked = []() { const char *e = getenv("IMK_CONV_PIPE"); if (e && e[0] == '0') g_use_pipe = false; return true; }();
-    (void)env_checked;
-    const bool pipe_ok = g_use_pipe && pipe_fits(a) && a.x.cs_in <= 16 && a.cout <= 16 && (a.x.lmode != LM_U8 || a.x.cin <= 4) &&
-                         (!a.pre_wpk || imk_pad8(a.pre_cout) <= 16);
-    a.pair = pipe_ok && pair_enabled() && a.cout <= 8;   // must mirror imk_conv_pair_layout
-    if (a.pre_wpk && !(pipe_ok && a.wpk2 && a.pre_bias && a.pre_sc && a.pre_sh && a.pre_cout > 0)) return IMK_EUNSUPPORTED;
+    const PipeChoice p = pipe_choice(a);
+    a.pair = p.pair;
+    if (a.pre_wpk && !(p.ok && a.wpk2 && a.pre_bias && a.pre_sc && a.pre_sh && a.pre_cout > 0)) return IMK_EUNSUPPORTED;
     if (a.wpk2 && a.pair && a.cout2 > 8) return IMK_EUNSUPPORTED;
     if (a.wpk2) {   // fused second stage (callers check imk_conv_can_chain / imk_conv_can_chain_tile)
         if (a.epi != EP_RELU || !a.out2 || !a.bias2 || a.cs_out2 % 8) return IMK_EUNSUPPORTED;
-        if (pipe_ok) return a.cout2 > 16 ? IMK_EUNSUPPORTED : launch_conv_pipe_any(a, stream);
+        if (p.ok) return a.cout2 > 16 ? IMK_EUNSUPPORTED : launch_conv_pipe_any(a, stream);
         if (!imk_conv_can_chain_tile(a, a.cout2, a.out != nullptr)) return IMK_EUNSUPPORTED;
         if (conv_wide_chain_ok(a)) return launch_conv_wide_chain(a, stream);
         if (imk_conv_gemm_chain_ok(a)) return imk_launch_conv_gemm(a, stream);
         return launch_conv_mfma(a, stream);
     }
-    if (pipe_ok) return launch_conv_pipe_any(a, stream);
+    if (p.ok) return launch_conv_pipe_any(a, stream);
     if (a.x.lmode == LM_STEM) return IMK_EUNSUPPORTED;
     if (conv_wide_ok(a)) return launch_conv_wide_any(a, stream);
     if (imk_conv_gemm_ok(a)) return imk_launch_conv_gemm(a, stream);
@@ -2517,7 +2459,7 @@ int imk_launch_conv(const ImkConvArgs &a_in, hipStream_t stream) {
 int imk_wgrad_splits(int B, int H, int W, int cin, int cout) {
     const int n_tiles = B * imk_cdiv(H, 16) * imk_cdiv(W, TW);
     const int n_pairs = ((imk_pad8(cin) + 15) / 16) * ((imk_pad8(cout) + 15) / 16);
-    static const int target = []() { const char *e = getenv("IMK_WGRAD_WGS"); return e ? atoi(e) : 768; }();
+    constexpr int target = 768;
     int s = target / n_pairs;   // ~3 resident workgroups per CU; each walks its tiles with prefetch
     if (s < 1) s = 1;
     if (s > n_tiles) s = n_tiles;
@@ -2586,8 +2528,7 @@ static double wgrad_algorithmic_bytes(const ImkWgradArgs &a, const WgradLaunch &
 
 int imk_launch_wgrad(const ImkWgradArgs &a, hipStream_t stream) {
     // the input block (uint8 image -> <= 8 channels, BatchNorm behind it): a streaming reduction, not a matrix-core kernel
-    static const bool stem_off = []() { const char *e = getenv("IMK_STEM_WGRAD"); return e && e[0] == '0'; }();
-    if (!stem_off && a.x.lmode == LM_U8 && a.ksize == 1 && a.dA_z && a.dA_coef && a.cs_out == 8 && a.x.cin <= 4 && a.n_split >= 1) {
+    if (a.x.lmode == LM_U8 && a.ksize == 1 && a.dA_z && a.dA_coef && a.cs_out == 8 && a.x.cin <= 4 && a.n_split >= 1) {
         const long long n_pix = (long long)a.B * a.H * a.W;
         ImkProfScope prof(PF_WGRAD, (double)n_pix * (a.x.cin + 32) + (double)a.n_split * 2 * 1024, stream, imk_wgrad_flops(a));
         imk_klaunch(stem_wgrad_kernel, dim3(a.n_split), dim3(256), 0, stream, reinterpret_cast<const uint8_t *>(a.x.in), a.x.cin, a.x.u8_div, a.dA, a.dA_z, a.dA_coef,

@@ -735,7 +735,7 @@ int imk_bn_prep_blocks(int B, int H, int W, int cs) {
     // (cap measured on the training step, ISIC / SUIM / HeLa / Cityscapes shapes: 4096 blocks -- one window or pixel pair per
     //  thread, every block resident and in the same phase at the same time -- 1.191 / 2.260 / 2.237 / 3.382 ms; 1024: 1.170;
     //  512: 1.167 / 2.230 / 2.204 / 3.344; 256: 1.168)
-    static const int cap = []() { const char *e = getenv("IMK_PREP_MAX_BLOCKS"); return e ? atoi(e) : 512; }();
+    constexpr int cap = 512;
     if (nb > cap) nb = cap;
     if (nb < 1) nb = 1;
     return (int)nb;
@@ -823,7 +823,7 @@ __global__ __launch_bounds__(256) void head_softmax_kernel(const f16 *__restrict
 
 static int launch_head_softmax(const f16 *z, const float *sc, const float *sh, const float *w, const float *bias, int cin, int cs,
                                int K, long long n_pix, float *probs, hipStream_t stream) {
-    static const int cap = []() { const char *e = getenv("IMK_HEAD_BLOCKS"); return e ? atoi(e) : 2048; }();
+    constexpr int cap = 2048;
     const long long want = (n_pix + 255) / 256;
     const int nb = (int)(want < cap ? want : cap);
     const size_t lds = (size_t)4 * 64 * K * sizeof(float);
@@ -870,9 +870,9 @@ int imk_launch_head(const f16 *z, const float *sc, const float *sh, const float 
     return IMK_OK;
 }
 
-// blocks of head_loss_kernel = rows of its loss partials: grid-stride over the pixels beyond IMK_HEAD_LOSS_BLOCKS blocks
+// blocks of head_loss_kernel = rows of its loss partials: grid-stride over the pixels beyond `cap` blocks
 int imk_loss_blocks(long long n_pix) {
-    static const int cap = []() { const char *e = getenv("IMK_HEAD_LOSS_BLOCKS"); return e ? atoi(e) : 1024; }();
+    constexpr int cap = 1024;
     const long long nb = (n_pix + 255) / 256;
     return (int)(nb > cap ? cap : nb);
 }

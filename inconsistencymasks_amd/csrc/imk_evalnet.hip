@@ -4,6 +4,7 @@
 // i.e. the U-Net's encoder block: its BatchNorm and pooling are applied by the consumer on load.
 // Plans are imk_unet_plan objects: parameter layout, packing, optimizer state and AdamW step are the imk_unet_* calls.
 #include "imk_net.h"
+#include "imk_switches.h"
 
 namespace {
 
@@ -229,10 +230,9 @@ extern "C" int imk_evalnet_fwd_bwd(const imk_unet_plan *plan, float *params, voi
     float *head_out = out ? out : reinterpret_cast<float *>(c.base + c.ws.probs);
     OK(run_head(c, t, head_out, y, sv.ctl, stats));
 
-    static const int n_side_env = []() { const char *s = getenv("IMK_SIDE_STREAMS"); int v = s ? atoi(s) : 1;
-                                         return v < 0 ? 0 : (v > imk_unet_plan::MAX_SIDE ? imk_unet_plan::MAX_SIDE : v); }();
-    const bool side_on = !plan->dbg_single_stream && n_side_env > 0 && ensure_side_streams(plan, n_side_env);
-    Bwd b{c, grads, sv.ctl, stats + 1, side_on ? n_side_env : 0, 1LL << 62};
+    const int n_side = imk_switches().side_streams;
+    const bool side_on = !plan->dbg_single_stream && n_side > 0 && ensure_side_streams(plan, n_side);
+    Bwd b{c, grads, sv.ctl, stats + 1, side_on ? n_side : 0};
     ImkStopRingScope stop_ring(plan, stream, b.n_side);      // the backward pass's launches carry their own events (imk_common.h)
     {   // Dense gradients and the loss values: batch reduction of the head kernel's per-sample terms
         const ImkLayer &d0 = plan->layers[t.dense[0]];
@@ -254,12 +254,10 @@ extern "C" int imk_evalnet_fwd_bwd(const imk_unet_plan *plan, float *params, voi
     const int csF = imk_pad8(e.ch[0]);
     for (int s = 1; s >= 0; --s) {
         const f16 *dcat = reinterpret_cast<const f16 *>(c.base + c.ws.dcat) + s * csF;
-        {   // IMK_EVALNET_TAIL: 0 = round 4's order; 1 = the last tower's weight gradients released with their dgrads and their split
-            // reductions left to the end of the step (Bwd::tail_early, Bwd::defer_finalize); 2 (default) = both towers released early
-            static const int tail = []() { const char *e = getenv("IMK_EVALNET_TAIL"); return e ? atoi(e) : 2; }();
-            if (tail >= 2 || (tail == 1 && s == 0)) b.tail_early = true;
-            if (tail >= 1 && s == 0) b.defer_finalize = true;
-        }
+        // both towers' weight gradients released with their dgrads (Bwd::tail_early), the last tower's split reductions left to
+        // the end of the step (Bwd::defer_finalize)
+        b.tail_early = true;
+        if (s == 0) b.defer_finalize = true;
         OK(b.bn_bwd(t.t_bn[s], 1, nullptr, dcat, 2 * csF));
         OK(b.wgrad_dgrad(t.t_c1[s], c.dA(t.t_c3[s]), c.act(t.t_c3[s])));
         OK(b.wgrad_dgrad(t.t_c3[s], c.dy(t.in_bn[s]), nullptr, t.in_bn[s]));

@@ -28,6 +28,7 @@
 #include <cstdlib>
 #include <type_traits>
 #include "imk_stage.h"
+#include "imk_switches.h"
 
 IMK_STAMP_TABLE(gemm)
 
@@ -480,11 +481,6 @@ __global__ __launch_bounds__(256, 2) void conv_gemm_kernel(ImkConvArgs a, GemmGe
 
 inline int odd_up(int v) { return v | 1; }
 
-bool gemm_env_on() {
-    static const bool on = []() { const char *e = getenv("IMK_CONV_GEMM"); return !(e && e[0] == '0'); }();
-    return on;
-}
-
 int plan_conv_gemm(const ImkConvArgs &a, GemmGeom &gm, int &pn, size_t &lds, int &grid) {
     const int nc8 = a.x.cs_in / 8;
     const int nc8p = imk_pass_chunks(nc8), n_pass = imk_cdiv_d(nc8, nc8p);
@@ -497,8 +493,6 @@ int plan_conv_gemm(const ImkConvArgs &a, GemmGeom &gm, int &pn, size_t &lds, int
     // output channels per workgroup: 128 or 64, whichever pads less (ties: the larger tile, one read of the input fewer)
     const int g128 = imk_cdiv_d(mt_total, 8), g64 = imk_cdiv_d(mt_total, 4);
     pn = (g128 * 8 <= g64 * 4) ? 4 : 2;
-    static const int force_pn = []() { const char *e = getenv("IMK_GEMM_PN"); return e ? atoi(e) : 0; }();
-    if (force_pn == 2 || (force_pn == 4 && mt_total > 4)) pn = force_pn;
     if (a.wpk2) {            // chained 1x1: one workgroup holds every output channel of its pixels
         pn = mt_total > 4 ? 4 : 2;
         const int nc8_2 = a.cs_out / 8;
@@ -520,25 +514,17 @@ int plan_conv_gemm(const ImkConvArgs &a, GemmGeom &gm, int &pn, size_t &lds, int
     if (lds < out_bytes) lds = out_bytes;
     if (lds < red_bytes) lds = red_bytes;
     if (lds > 64 * 1024) return IMK_EUNSUPPORTED;
-    // workgroups per compute unit: capped by padding the LDS request (160 KB / w), IMK_GEMM_W = 2 / 3 / 4 (0: what fits)
-    static const int force_w = []() { const char *e = getenv("IMK_GEMM_W"); return e ? atoi(e) : 0; }();
-    if (force_w >= 1 && force_w <= 3) {
-        const size_t want = (size_t)160 * 1024 / (force_w + 1) + 1024;
-        if (lds < want && want <= 64 * 1024) lds = want;
-    }
+    // workgroups per compute unit: what fits (capping them by padding the LDS request was measured and not kept: DESIGN.md)
     grid = imk_cdiv_d(gm.n_sp, 8) * 8 * gm.gy;
     return IMK_OK;
 }
 
 // launches of at most this many workgroups take the deep-look-ahead form (AD > 1): few workgroups per compute unit are resident,
-// nothing else hides the weight fragments' L2 round trip (IMK_GEMM_AD3_WGS; 0 = never).  Measured on one box (profiles/r06_ab_ad3.txt),
+// nothing else hides the weight fragments' L2 round trip (ImkSwitches::gemm_ad3_wgs; 0 = never).  Measured on one box (profiles/r06_ab_ad3.txt),
 // training step old -> 512 / 1 024 / 1 600 / 6 000: ISIC 0.958 -> 0.930 / 0.936 / 0.943 / 0.936 ms, SUIM 1.630 -> 1.593 / 1.593 / 1.600 /
 // 1.596, HeLa 1.61 -> 1.588 / 1.584 / 1.593 / 1.592, EvalNet 2.04 -> 2.004 / 1.997 / 1.997 / 1.995, Cityscapes alpha 2 4.63 -> 4.618 /
 // 4.616 / 4.608 / 4.613, alpha 1.25 3.61 -> 3.619 / 3.619 / 3.618 / 3.677: bit-identical everywhere
-int gemm_ad3_max_wgs() {
-    static const int v = []() { const char *e = getenv("IMK_GEMM_AD3_WGS"); return e ? atoi(e) : 1024; }();
-    return v;
-}
+int gemm_ad3_max_wgs() { return imk_switches().gemm_ad3_wgs; }
 
 // ring depth of the deep-look-ahead form per load mode: what fits 256 registers without scratch (pool / upsample + add on load hold
 // 4 / 2 raw chunks per staged item)
@@ -599,7 +585,7 @@ int launch_conv_gemm_k(const ImkConvArgs &a, const GemmGeom &gm, int pn, size_t 
 // Which launches the GEMM-class kernel takes: more than 32 channels on a side (the per-tile kernel's layers), plain
 // (unchained) convs whose input is a fp16 tensor.
 bool imk_conv_gemm_ok(const ImkConvArgs &a) {
-    if (!gemm_env_on()) return false;
+    if (!imk_switches().conv_gemm) return false;
     if (a.wpk2 || a.pre_wpk || a.wg_partial) return false;
     // (Round 5, measured and removed: the pooled-input 3x3 with 16 -> 32 channels -- the second encoder block at alpha 1, the third at
     //  alpha 0.5; on the per-tile kernel the largest single item of an alpha = 1 inference call, 1.0-1.2 TB/s -- on THIS kernel with
@@ -622,10 +608,7 @@ bool imk_conv_gemm_ok(const ImkConvArgs &a) {
 // one row per workgroup over the same 128 pixels, summed in the order of the 1x1's own launch (see `finish`): bit-identical to
 // two launches
 bool imk_conv_gemm_chain_ok(const ImkConvArgs &a) {
-    static const bool off = []() { const char *e = getenv("IMK_GEMM_CHAIN"); return e && e[0] == '0'; }();
-    static const bool train_off = []() { const char *e = getenv("IMK_GEMM_CHAIN_TRAIN"); return e && e[0] == '0'; }();
-    if (off || !a.wpk2 || !a.out2 || a.epi != EP_RELU || a.ksize != 3) return false;
-    if ((a.out || a.stats_partial) && train_off) return false;      // training: the intermediate is stored, statistics on the 1x1's output
+    if (!imk_switches().gemm_chain || !a.wpk2 || !a.out2 || a.epi != EP_RELU || a.ksize != 3) return false;
     if (a.x.lmode != LM_POOL && a.x.lmode != LM_AFFINE) return false;
     if (a.cout > 128 || a.cout2 > 128 || a.cs_out2 > (a.cout > 64 ? 128 : 64)) return false;
     ImkConvArgs plain = a;

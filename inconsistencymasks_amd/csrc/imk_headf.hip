@@ -417,12 +417,11 @@ __global__ __launch_bounds__(256) void head_mse_fused_kernel(HeadCceArgs a) {
 }  // namespace
 
 // Sigmoid heads with one map on 8 (padded) channels: ISIC at alpha 0.5, the headline shape.  Measured per training step
-// (tests/gpu_probe/ab_env.sh, off / on): ISIC alpha 0.5 1.007 / 0.983 ms; the wider forms hold their 2 CS + CS K + K + 1
+// (without / with this kernel): ISIC alpha 0.5 1.007 / 0.983 ms; the wider forms hold their 2 CS + CS K + K + 1
 // accumulators in 215-256 registers (two waves per SIMD) and lose -- ISIC alpha 1 (16 channels, 1 map) 1.674 / 1.684, HeLa
 // (16 channels, 3 maps) 1.673 / 1.745 -- so they keep head_loss_kernel + the pipelined dgrad.  rows_cap as below.
 bool imk_head_mse_fused_ok(int cs, int K, long long n_pix, int rows_cap) {
-    static const bool off = []() { const char *e = getenv("IMK_HEAD_MSE_FUSE"); return e && e[0] == '0'; }();
-    if (off || cs != 8 || K != 1) return false;
+    if (cs != 8 || K != 1) return false;
     return imk_loss_blocks(n_pix) <= rows_cap;
 }
 
@@ -440,8 +439,7 @@ int imk_launch_head_mse_fused(const f16 *z, const float *sc, const float *sh, co
 
 // Softmax heads with 8 ... 32 (padded) input channels and up to 64 classes.  `rows_cap`: capacity (rows) of dystat_partial.
 bool imk_head_cce_fused_ok(int cs, int K, long long n_pix, int rows_cap) {
-    static const bool off = []() { const char *e = getenv("IMK_HEAD_FUSE"); return e && e[0] == '0'; }();
-    if (off || (cs != 8 && cs != 16 && cs != 24 && cs != 32) || K < 2 || K > 64) return false;
+    if ((cs != 8 && cs != 16 && cs != 24 && cs != 32) || K < 2 || K > 64) return false;
     return imk_loss_blocks(n_pix) <= rows_cap;
 }
 

@@ -270,10 +270,6 @@ inline int run_conv_pre_pair(Ctx &c, int pre, int c3, int c1) {
         if (!imk_conv_can_chain(plain, l2.cout)) return IMK_EUNSUPPORTED;
     }
     if (!imk_conv_can_prestage(a, lp.lmode, lp.cin, lp.cout)) return IMK_EUNSUPPORTED;
-#ifdef IMK_PRE_DEBUG
-    a.out = c.act(c3);                              // probe build: first-stage dumps land in the (otherwise unused) d.c3 / d.ca tensors
-    a.mask = c.act(pre);
-#endif
     a.pre_wpk = c.wfwd(pre);
     a.pre_bias = c.params + lp.off_b;
     a.pre_sc = c.bn_scale(lp.bn_after); a.pre_sh = c.bn_shift(lp.bn_after);
@@ -303,7 +299,6 @@ struct Bwd {
     ImkCtl *ctl;
     float *found_inf;       // = stats + 1: set to 1 by any gradient kernel that sees a non-finite value
     int n_side;             // side streams in use (0: everything on c.stream); weight-gradient work is dealt round-robin
-    long long side_max_pixels;   // layers with at most this many pixels run their wgrad on a side stream
     ImkWgFinalJobs jobs{};
     int n_fork = 0;
     bool used_side[imk_unet_plan::MAX_SIDE] = {};
@@ -393,7 +388,7 @@ struct Bwd {
         // The pooled-input 3x3 form of the kernel holds 162 VGPRs: three workgroups per CU would leave the backward chain's next
         // kernel no registers to start in (see wgrad_mfma_body: KS3), so it runs with two
         if (l.ksize == 3 && l.lmode == LM_POOL) {
-            static const int pool_wgs = []() { const char *e = getenv("IMK_WGRAD_POOL_WGS"); return e ? atoi(e) : 512; }();
+            constexpr int pool_wgs = 512;
             const int n_pairs = ((imk_pad8(l.cin) + 15) / 16) * ((imk_pad8(l.cout) + 15) / 16);
             a.n_split = std::max(1, std::min(a.n_split, pool_wgs / n_pairs));
         }
@@ -432,10 +427,8 @@ struct Bwd {
     // queued for finish_wgrads, which launches it on the main stream -- no fork and no join in the step's tail
     int wgrad(int conv, const f16 *dA_override = nullptr, bool last = false) {
         const ImkLayer &l = c.p->layers[conv];
-        const Dim d = res_dim(c.p->cfg, l.res);
-        const bool small = (long long)c.B * d.h * d.w <= side_max_pixels;
-        if (n_side > 0 && small && conv == hold_conv) { held = Pending{conv, dA_override}; has_held = true; return IMK_OK; }
-        if (n_side > 0 && small) {
+        if (n_side > 0 && conv == hold_conv) { held = Pending{conv, dA_override}; has_held = true; return IMK_OK; }
+        if (n_side > 0) {
             if (n_pending == 8) { int rc = flush_wgrads(); if (rc) return rc; }
             pending[n_pending++] = Pending{conv, dA_override};
             // full-resolution layers: fork at once -- their kernels are long (the bubble is small against them) and the
@@ -444,14 +437,9 @@ struct Bwd {
         }
         return launch_wgrad(conv, dA_override, c.stream);
     }
-    // End of a resolution block below full resolution: its weight gradients go to the side stream -- every block (IMK_FORK_EVERY=1,
-    // the default) or every k-th one (each fork is an event record on the main stream: ~6 us before the chain's next kernel starts).
-    int n_block_flush = 0;
-    int flush_block() {
-        static const int every = []() { const char *e = getenv("IMK_FORK_EVERY"); const int v = e ? atoi(e) : 1; return v < 1 ? 1 : v; }();
-        if (++n_block_flush % every != 0 && n_pending <= 4) return IMK_OK;
-        return flush_wgrads();
-    }
+    // End of a resolution block below full resolution: its weight gradients go to the side stream -- every block (forking only
+    // every k-th one, each fork an event record on the main stream, was measured and not kept: DESIGN.md).
+    int flush_block() { return flush_wgrads(); }
     int flush_wgrads() {
         if (n_pending == 0) return IMK_OK;
         const int si = n_fork % n_side;
@@ -541,15 +529,12 @@ struct Bwd {
         }
         // Full resolution: the weight gradient is released when the dgrad beside it has FINISHED, not when it starts -- both
         // are bandwidth-bound there, and the dgrad is the one the chain waits for (step -0.9 %, SUIM -1.4 %, HeLa -1.2 %; the
-        // same at the lower levels changes nothing).  IMK_FORK_LATE = highest level released late (-1: none).
+        // same at the lower levels changes nothing).
         // Round 5, after the input block's streaming weight gradient and the narrower staging maps: at <= 16 channels the early release
         // wins again (ISIC 0.984 -> 0.967 ms, SUIM 1.664 -> 1.647, HeLa -0.5 %, Cityscapes alpha 1 -0.9 %), from 24 channels up the late
-        // one still does (Cityscapes alpha 1.5 / 2, ISIC alpha 1.5: +0.7-1 % released early) -- the rule follows the layer's width
-        // unless IMK_FORK_LATE is set.
-        static const bool late_set = getenv("IMK_FORK_LATE") != nullptr;
-        static const int late_res = []() { const char *e = getenv("IMK_FORK_LATE"); return e ? atoi(e) : 0; }();
+        // one still does (Cityscapes alpha 1.5 / 2, ISIC alpha 1.5: +0.7-1 % released early) -- the rule follows the layer's width.
         const bool wide = imk_pad8(l.cin) >= 24 || imk_pad8(l.cout) >= 24;
-        if (l.res <= late_res && !tail_early && (wide || late_set)) {
+        if (l.res == 0 && !tail_early && wide) {
             int rc = dgrad(conv, dst, mask, stat_bn, s2_bn);
             if (rc) return rc;
             return wgrad(conv);
@@ -568,11 +553,6 @@ struct Bwd {
         n_pending = 0;
         for (int si = 0; si < n_side; ++si) {   // join: the reductions below read the side streams' partials
             if (!used_side[si]) continue;
-            ImkStopRing *ring = imk_tls_stop_ring;
-            if (ring && ring->stream == c.stream && ring->side == c.p->side[si] && ring->side_last) {
-                IMK_HIP(hipStreamWaitEvent(c.stream, ring->side_last, 0));      // the side stream's last kernel's own event
-                continue;
-            }
             IMK_HIP(hipEventRecord(c.p->ev_join[si], c.p->side[si]));
             IMK_HIP(hipStreamWaitEvent(c.stream, c.p->ev_join[si], 0));
         }
@@ -606,19 +586,16 @@ struct Bwd {
 };
 
 // Installs the plan's stop-event ring for `stream` on this thread for the lifetime of the object (a training step's backward pass).
-// IMK_STOP_EVENTS=0: forks record events of their own, as rounds 2-4 did.
+// The forks wait for kernel-bound events; the join at the end of the step records its own.  Measured (one box, four repetitions;
+// forks recording their own events, as rounds 2-4 did / this / the join on a kernel-bound event as well): ISIC step 0.964 / 0.954 /
+// 0.957 ms, SUIM 1.631 / 1.614 / 1.620, EvalNet 2.037 / 2.027 / 2.025.
 struct ImkStopRingScope {
     ImkStopRing ring{};
     ImkStopRing *prev = nullptr;
     bool on = false;
     ImkStopRingScope(const imk_unet_plan *plan, hipStream_t stream, int n_side) {
-        const bool want = n_side > 0;
-        // IMK_STOP_EVENTS: 0 = off, 1 (default) = the forks wait for kernel-bound events, 2 = the join at the end of the step as well
-        // (one box, four repetitions: ISIC step 0.964 / 0.954 / 0.957 ms, SUIM 1.631 / 1.614 / 1.620, EvalNet 2.037 / 2.027 / 2.025)
-        static const int mode = []() { const char *e = getenv("IMK_STOP_EVENTS"); return e ? atoi(e) : 1; }();
-        if (!want || mode <= 0 || !plan->ev_ring[0]) return;
+        if (n_side <= 0 || !plan->ev_ring[0]) return;
         ring = ImkStopRing{plan->ev_ring, 128, 0, stream, nullptr};
-        if (n_side == 1 && mode >= 2) ring.side = plan->side[0];
         prev = imk_tls_stop_ring;
         imk_tls_stop_ring = &ring;
         on = true;

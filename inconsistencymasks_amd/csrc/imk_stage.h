@@ -301,12 +301,11 @@ inline unsigned imk_div_magic(int d) { return d > 1 ? (unsigned)((1ull << 32) / 
 // 1.6 ms to a 0.9 ms forward); 32 groups = 4 per XCD on separate lines keep the take off the critical path.
 // (IMK_SCHED_HEADS / IMK_SCHED_STRIDE / IMK_SCHED_BYTES: imk_kernels.h)
 inline ImkWalk imk_walk_make(int &grid, int n_tiles, int per_img, bool dyn = false) {
-    static const bool off = []() { const char *e = getenv("IMK_XCD_WALK"); return e && e[0] == '0'; }();
     ImkWalk w{};
     if (dyn && grid >= 64 && n_tiles >= 64) {     // 32 groups: group & 7 = XCD, group >> 3 = quarter of that XCD's range
         grid &= ~31;
         w.shift = 5; w.chunk = (n_tiles + 31) / 32; w.step = grid / 32;
-    } else if (!off && grid >= 64 && n_tiles >= 64) {
+    } else if (grid >= 64 && n_tiles >= 64) {
         grid &= ~7;
         w.shift = 3; w.chunk = (n_tiles + 7) / 8; w.step = grid / 8;
     } else {

@@ -6,6 +6,7 @@
 #include <cstdio>
 #include "imk_net.h"
 #include "imk_head.h"
+#include "imk_switches.h"
 
 namespace {
 
@@ -350,8 +351,7 @@ static int run_ensemble_forwards(const imk_unet_plan *plan, const Topo &topo, co
     int n_slabs = (int)(((size_t)workspace_bytes - slab * n_models) / ws.total);
     if (n_slabs > n_models) n_slabs = n_models;
     if (n_slabs > max_streams) n_slabs = max_streams;
-    static const bool conc_off = []() { const char *e = getenv("IMK_ENSEMBLE_STREAMS"); return e && e[0] == '0'; }();
-    if (n_slabs > 1 && (conc_off || plan->dbg_single_stream || !ensure_side_streams(plan, n_slabs - 1))) n_slabs = 1;
+    if (n_slabs > 1 && (plan->dbg_single_stream || !ensure_side_streams(plan, n_slabs - 1))) n_slabs = 1;
     if (n_slabs > 1) {
         IMK_HIP(hipEventRecord(plan->ev_fork[0], main_stream));
         for (int s = 1; s < n_slabs; ++s) IMK_HIP(hipStreamWaitEvent(plan->side[s - 1], plan->ev_fork[0], 0));
@@ -394,8 +394,7 @@ extern "C" int imk_unet_forward_im(const imk_unet_plan *plan, int n_models, cons
     ha.batch = batch; ha.hw = cf.h * cf.w; ha.thr = thr; ha.cmp_ge = cmp_ge; ha.img = img; ha.c = cf.c_in;
     ha.block_in = block_in; ha.block_out = block_out; ha.img_out = img_out; ha.masks_out = masks_out; ha.im_out = im_out;
     ha.im_size = im_size; ha.pred_size = pred_size; ha.presence = presence;
-    static const bool fuse_off = []() { const char *e = getenv("IMK_HEAD_IM_FUSE"); return e && e[0] == '0'; }();
-    bool fused = !fuse_off && !plan->dbg_materialize && imk_head_im_supported(ha) &&
+    bool fused = !plan->dbg_materialize && imk_head_im_supported(ha) &&
                  (int64_t)(head_slab_bytes(plan, batch, true) * n_models + ws.total) <= workspace_bytes;
     const size_t slab = head_slab_bytes(plan, batch, fused);
     if ((int64_t)(slab * n_models + ws.total) > workspace_bytes) return IMK_EWORKSPACE;
@@ -495,12 +494,10 @@ extern "C" int imk_unet_fwd_bwd(const imk_unet_plan *plan, float *params, void *
     // The weight-gradient kernels run on a side stream, forked after the kernel that produced their gradient operand and
     // joined before the final reduction: nothing on the backward chain depends on them, and they fill the gaps that the
     // latency-bound kernels of the chain leave (1.280 vs 1.365 ms per step with all 24 on the side stream; forking only
-    // the deep layers' was neutral).  IMK_SIDE_PIXELS = largest B*H*W that is forked (0: single stream).
-    static const long long side_px = []() { const char *e = getenv("IMK_SIDE_PIXELS"); return e ? atoll(e) : (1LL << 62); }();
-    static const int n_side_env = []() { const char *e = getenv("IMK_SIDE_STREAMS"); int v = e ? atoi(e) : 1;
-                                         return v < 0 ? 0 : (v > imk_unet_plan::MAX_SIDE ? imk_unet_plan::MAX_SIDE : v); }();
-    const bool side_on = side_px > 0 && !plan->dbg_single_stream && n_side_env > 0 && ensure_side_streams(plan, n_side_env);
-    Bwd b{c, grads, sv.ctl, stats + 1, side_on ? n_side_env : 0, side_px};
+    // the deep layers' was neutral).
+    const int n_side = imk_switches().side_streams;
+    const bool side_on = !plan->dbg_single_stream && n_side > 0 && ensure_side_streams(plan, n_side);
+    Bwd b{c, grads, sv.ctl, stats + 1, side_on ? n_side : 0};
     ImkStopRingScope stop_ring(plan, stream, b.n_side);      // from here on: the backward pass's launches carry their own events
     bool loss_done = false;
     auto loss_on_side = [&]() -> int {      // once, as soon as a fork exists (every fork event is younger than the head's kernel)
@@ -575,8 +572,7 @@ extern "C" int imk_unet_fwd_bwd(const imk_unet_plan *plan, float *params, void *
     for (int i = 3; i >= 0; --i) {
         if (i == 0) {
             b.defer_finalize = true;   // last block: nothing left to hide its split reductions behind
-            static const bool swap_off = []() { const char *e = getenv("IMK_TAIL_SWAP"); return e && e[0] == '0'; }();
-            if (!swap_off) b.hold_conv = t.e_c3[0];
+            b.hold_conv = t.e_c3[0];
         }
         OK(b.bn_bwd(t.e_bn[i], 1, reinterpret_cast<f16 *>(c.base + c.ws.dU[3 - i]),
                     reinterpret_cast<f16 *>(c.base + c.ws.dP[i])));

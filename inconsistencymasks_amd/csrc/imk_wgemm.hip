@@ -10,15 +10,11 @@
 // Reference: the Conv2D kernel / bias gradients inside model.fit (functions.py:218) of unet.py:11-43 and evalnet.py:8-21.
 #include <cstdlib>
 #include "imk_stage.h"
+#include "imk_switches.h"
 
 IMK_STAMP_TABLE(wgemm)
 
 namespace {
-
-bool gemm_env_on() {
-    static const bool on = []() { const char *e = getenv("IMK_CONV_GEMM"); return !(e && e[0] == '0'); }();
-    return on;
-}
 
 // =====================================================================================================
 // weight gradient of the wide layers
@@ -230,15 +226,18 @@ __global__ __launch_bounds__(256, NFO == 2 ? 3 : 2) void wgrad_gemm_kernel(ImkWg
 namespace {
 struct WgGemmPlan { WgGemmGeom gm; int nfi_t, kp, n_split; size_t lds; };
 
-bool wgemm_env_on() {
-    static const bool on = []() { const char *e = getenv("IMK_WGRAD_GEMM"); return !(e && e[0] == '0'); }();
-    return on && gemm_env_on();
-}
-
-bool wgrad_nfo2_on() {
-    static const bool on = []() { const char *e = getenv("IMK_WGRAD_NFO2"); return !(e && e[0] == '0'); }();
-    return on;
-}
+// workgroups a launch is sized for: its split count is the largest that gives every (input group, output group) pair this many
+// in all (x 3/2 for the two-output-tile form)
+constexpr int WGRAD_GEMM_WGS = 512;
+// Every workgroup ends by writing its accumulators (148 KB at 64 x 64 channels x 9 taps): with few tiles per workgroup those
+// partials -- and the split reduction that reads them back -- outweigh the operands, so a workgroup gets at least this many
+// pixel tiles (the deep levels then run on fewer workgroups than the chip has slots: they are short)
+constexpr int WGRAD_GEMM_MIN_TILES = 8;
+// Few 16 x 16 channel pairs AND few pixels (the deep levels at alpha = 0.5): the per-pair kernel of imk_conv.hip already
+// spreads such a layer over 768 workgroups with little re-reading, and this one would run on 16-64 (ISIC step 1.014 vs 1.050 ms);
+// with many pairs (alpha >= 1: 64-512 pairs at the same pixel counts) it re-reads both operands per pair and this kernel wins
+constexpr int WGRAD_GEMM_MIN_PAIRS = 17;
+constexpr long long WGRAD_GEMM_MIN_PIXELS = 100000;
 
 void plan_wgrad_gemm(int lmode, int B, int H, int W, int ksize, int cs_in, int cs_out, WgGemmPlan &P) {
     WgGemmGeom &gm = P.gm;
@@ -255,15 +254,10 @@ void plan_wgrad_gemm(int lmode, int B, int H, int W, int ksize, int cs_in, int c
     const int halo = ksize == 3 ? 1 : 0;
     gm.tiles_x = imk_cdiv(W, TW); gm.tiles_y = imk_cdiv(H, tr);
     gm.n_tiles = B * gm.tiles_x * gm.tiles_y;
-    static const int target = []() { const char *e = getenv("IMK_WGRAD_GEMM_WGS"); return e ? atoi(e) : 512; }();
-    // Every workgroup ends by writing its accumulators (148 KB at 64 x 64 channels x 9 taps): with few tiles per workgroup those
-    // partials -- and the split reduction that reads them back -- outweigh the operands, so a workgroup gets at least
-    // IMK_WGRAD_GEMM_TILES pixel tiles (the deep levels then run on fewer workgroups than the chip has slots: they are short)
-    static const int min_tiles = []() { const char *e = getenv("IMK_WGRAD_GEMM_TILES"); return e ? atoi(e) : 8; }();
     // the two-output-tile form of the 3x3 (wgrad_gemm_kernel<.., 2, 2>) runs 3 workgroups per compute unit
-    const bool nfo2 = wgrad_nfo2_on() && lmode == LM_AFFINE && ksize == 3 && P.nfi_t == 2 && gm.cot_n <= 2;
-    int ns = (nfo2 ? target * 3 / 2 : target) / (gm.gi_n * gm.go_n);
-    const int mt = min_tiles * 64 / (tr * 16) > 1 ? min_tiles * 64 / (tr * 16) : 1;       // counted in 64-pixel tiles
+    const bool nfo2 = imk_switches().wgrad_nfo2 && lmode == LM_AFFINE && ksize == 3 && P.nfi_t == 2 && gm.cot_n <= 2;
+    int ns = (nfo2 ? WGRAD_GEMM_WGS * 3 / 2 : WGRAD_GEMM_WGS) / (gm.gi_n * gm.go_n);
+    const int mt = WGRAD_GEMM_MIN_TILES * 64 / (tr * 16) > 1 ? WGRAD_GEMM_MIN_TILES * 64 / (tr * 16) : 1;       // counted in 64-pixel tiles
     if (ns > gm.n_tiles / mt) ns = gm.n_tiles / mt;
     if (ns < 1) ns = 1;
     P.n_split = ns;
@@ -281,7 +275,7 @@ template <int LM, bool BNB, bool KS3>
 int launch_wgrad_gemm_k(const ImkWgradArgs &a, const WgGemmPlan &P, hipStream_t stream) {
     const dim3 grid(P.n_split, P.gm.gi_n * P.gm.go_n);
     if constexpr (LM == LM_AFFINE && KS3 && !BNB) {
-        if (wgrad_nfo2_on() && P.nfi_t == 2 && P.gm.cot_n <= 2) {
+        if (imk_switches().wgrad_nfo2 && P.nfi_t == 2 && P.gm.cot_n <= 2) {
             imk_klaunch(wgrad_gemm_kernel<LM, BNB, KS3, 2, 2>, dim3(grid), dim3(256), P.lds, stream, a, P.gm);
             return IMK_OK;
         }
@@ -298,20 +292,15 @@ int launch_wgrad_gemm_k(const ImkWgradArgs &a, const WgGemmPlan &P, hipStream_t 
 // step 6.20 -> 5.98 ms; at half resolution -- alpha = 1 -- the 16 x 16-channel kernel of imk_conv.hip is faster: 2.64 vs 2.69 ms).
 // IMK_WGRAD_GEMM_MIN overrides the channel threshold for every size.
 bool imk_wgrad_gemm_wide(int cs_in, int cs_out, long long pixels) {
-    static const int v = []() { const char *e = getenv("IMK_WGRAD_GEMM_MIN"); return e ? atoi(e) : 0; }();
+    const int v = imk_switches().wgrad_gemm_min;
     const int c = cs_in > cs_out ? cs_in : cs_out;
     if (v > 0) return c >= v;
     return c > 32 || (c >= 24 && pixels >= (2ll << 20));     // (24 ... 31: alpha 1.25 / 1.5 at full resolution: step 4.11 -> 4.05 / 4.29 -> 4.20 ms)
 }
 bool imk_wgrad_gemm_ok(int lmode, bool bnb, int ksize, int cs_in, int cs_out, long long pixels) {
-    if (!wgemm_env_on()) return false;
+    if (!imk_switches().conv_gemm) return false;
     if (!imk_wgrad_gemm_wide(cs_in, cs_out, pixels)) return false;
-    // Few 16 x 16 channel pairs AND few pixels (the deep levels at alpha = 0.5): the per-pair kernel of imk_conv.hip already
-    // spreads such a layer over 768 workgroups with little re-reading, and this one would run on 16-64 (ISIC step 1.014 vs 1.050 ms);
-    // with many pairs (alpha >= 1: 64-512 pairs at the same pixel counts) it re-reads both operands per pair and this kernel wins
-    static const int min_pairs = []() { const char *e = getenv("IMK_WGRAD_GEMM_PAIRS"); return e ? atoi(e) : 17; }();
-    static const long long min_pix = []() { const char *e = getenv("IMK_WGRAD_GEMM_PIX"); return e ? atoll(e) : 100000; }();
-    if (((cs_in + 15) / 16) * ((cs_out + 15) / 16) < min_pairs && pixels < min_pix) return false;
+    if (((cs_in + 15) / 16) * ((cs_out + 15) / 16) < WGRAD_GEMM_MIN_PAIRS && pixels < WGRAD_GEMM_MIN_PIXELS) return false;
     return wgrad_gemm_combo(lmode, bnb, ksize);
 }
 
