@@ -3,7 +3,7 @@
 one U-Net training epoch) on synthetic data of a BASELINE.json shape.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak] [--config isic|suim|cityscapes|hela] [--alpha A]
-                    [--dump-outputs DIR]
+                    [--dump-outputs DIR] [--full]
 
 Default = the configuration the metric is quoted on (BASELINE.json configs[1]): ISIC-2018-shaped 256x256x3, 2-model
 ensemble, alpha = 0.5.  --config picks one of the other shapes (configs[2..4]); --alpha overrides the width (the IM+
@@ -23,12 +23,18 @@ One "step" = one IM generation:
 Inputs are resident in HBM when the timed region starts (PNG decode/encode is excluded on both the GPU and
 the CPU side).
 
+A plain run sets up, warms up, times the steps, writes --dump-outputs if asked and prints its record as one JSON line: the
+headline (metric, value, unit, ms_per_step, ...), config and stage_ms.  --full measures and checks the rest after the same
+timed steps: roofline and per-kernel figures, the sharding check, the CPU baseline, PNG rates and, for the default command,
+the other BASELINE shapes; its last line is then a compact record that points to the full one.  The timed steps are the same
+either way (the sampled launch events and stage markers of the roofline included), so the headline means the same in both.
+
 Multi-GPU, default `--scaling strong` (the north star: "shard the unlabeled image set across the GPUs"): ONE
 set; rank r runs inference + IM on its contiguous block of the sorted set (functions.shard_list, no
 collective) and trains on its own kept pairs + its block of the labelled set with batch 32 per GPU, one all-reduce of
 the flat fp32 gradient buffer per step (RCCL), epoch steps = images // (32 * N).  value = images / time per generation.
-After the timed region rank 0 recomputes the IM stage over the WHOLE set and checks that the ranks' summed IM size,
-prediction size and kept count equal it (sharding does not change a single mask).
+With --full, after the timed region rank 0 recomputes the IM stage over the WHOLE set and checks that the ranks' summed IM
+size, prediction size and kept count equal it (sharding does not change a single mask).
 `--scaling weak`: every rank owns a full-size set (value = N * images / time).
 IMK_FORCE_DIST=1 with --gpus 1: a real one-rank process group (backend nccl = RCCL), so that init, the flat all-reduce
 and the barrier of the N-rank path execute on one GPU.
@@ -563,7 +569,11 @@ def main():
                          "pseudo-labels / IMs, the trained student's parameters) as DIR/<name>.npy, e.g. DIR = bench_outputs/<build> (rank 0, "
                          "the requested configuration only)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default run (isic, 1 GPU) only: skip the short runs of the other BASELINE shapes appended as other_configs")
+                    help="default --full run (isic, 1 GPU) only: skip the short runs of the other BASELINE shapes appended as other_configs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check what the headline does not need: roofline, per-kernel totals, "
+                         "exclusive pass, IM kernel alone, sharding check, CPU baseline with its parity sample, PNG rates, other_configs; "
+                         "the last line becomes the compact record and the full record goes to --detail")
     args = ap.parse_args()
     if args.provenance:       # before anything touches the GPU
         print(json.dumps({"bench_py_sha16": bench_py_sha16(), "lib_build_id": lib_build_id(), "round": ROUND}))
@@ -606,10 +616,10 @@ def main():
     n_gpus = dist.get_world_size() if use_dist else 1
     env = dict(rank=rank, world=world, dev=dev, dist=dist, use_dist=use_dist, n_gpus=n_gpus)
     out = run_config(args, args.config, args.alpha, env, primary=True)
-    # The other BASELINE shapes (configs[2..4] and the last IM+ width), two generations each, so that the one default command
-    # times them too: same generation(), same line fields (value, ms_per_step, stage_ms, roofline).  Only for the plain default
+    # The other BASELINE shapes (configs[2..4] and the last IM+ width), two generations each, so that the one default --full command
+    # times them too: same generation(), same line fields (value, ms_per_step, stage_ms, roofline).  Only for the default --full
     # run -- an explicit --config / --alpha / --images run stays what was asked for.
-    default_run = (world == 1 and not use_dist and args.config == "isic" and args.alpha is None and args.images is None
+    default_run = (args.full and world == 1 and not use_dist and args.config == "isic" and args.alpha is None and args.images is None
                    and args.labeled is None and not args.no_other_configs)
     if default_run:
         others = {}
@@ -632,10 +642,12 @@ def main():
                 others[key] = {"error": f"{type(e).__name__}: {e}"}
         out["other_configs"] = others
     if rank == 0 and out is not None:
-        detail = write_detail(out, args.detail)
-        line = compact_line(out, detail)
-        print(f"[bench] full record: {detail} ({len(json.dumps(out))} bytes); the line below: {len(json.dumps(line))} bytes",
-              file=sys.stderr, flush=True)
+        line = out               # a plain run's record is its line
+        if args.full:
+            detail = write_detail(out, args.detail)
+            line = compact_line(out, detail)
+            print(f"[bench] full record: {detail} ({len(json.dumps(out))} bytes); the line below: {len(json.dumps(line))} bytes",
+                  file=sys.stderr, flush=True)
         print(json.dumps(line), flush=True)
     if use_dist:
         dist.barrier()
@@ -858,6 +870,44 @@ def run_config(args, config_name, alpha, env, primary):
         print(f"[bench] outputs of the last timed step: {n_files} files, {n_bytes / 2**20:.1f} MB in {args.dump_outputs}",
               file=sys.stderr, flush=True)
         last_gen.clear()
+    t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+    if use_dist:
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+    elapsed = float(t.item())
+    t_inf = sum(a.elapsed_time(b) for a, b, _ in rec) / len(rec)
+    t_ep = sum(b.elapsed_time(c) for _, b, c in rec) / len(rec)
+    totals = torch.cat([totals, torch.tensor([float(info.pop("n_train"))], dtype=torch.float64, device=dev)])
+    if use_dist:
+        dist.all_reduce(totals)
+    n_all = U_total * (1 if strong else world)
+    info.update(kept=int(totals[2]), train_images=int(totals[3]), mean_pred_size=round(float(totals[0]) / n_all, 1),
+                mean_im_size=round(float(totals[1]) / n_all, 1))
+
+    out = None
+    if rank == 0:
+        n_images = U_total if strong else U_total * world
+        out = {
+            "metric": "images/sec per IM generation (ensemble infer + IM build + 1 train epoch), 256x256" if (H, W) == (256, 256)
+                      else f"images/sec per IM generation (ensemble infer + IM build + 1 train epoch), {H}x{W}",
+            "value": round(n_images * args.steps / elapsed, 2), "unit": "images/s", "n_gpus": n_gpus,
+            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1000 * elapsed / args.steps, 2),
+            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f16",
+            "data": "synthetic",
+            "config": {"workload": cfg["workload"], "name": config_name, "alpha": ALPHA, "shape": [H, W, C], "outputs": K,
+                       "unlabeled_images": n_images, "unlabeled_images_per_gpu": U,
+                       "labeled_images": L_total if strong else L_total * world,
+                       "n_models": N_MODELS, "infer_batch": infer_batch,
+                       "infer_batch_rule": "functions.infer_batch_size: 584 at alpha<=0.5 else 128; short tail spread" if not args.infer_batch else "--infer-batch",
+                       "train_batch_per_gpu": BATCH,
+                       "global_batch": BATCH * world, "parallelism": f"dp{world}",
+                       "bn_momentum": {"rule": bn_rule, "value": round(bn_mom, 6)},
+                       "process_group": (os.environ.get("IMK_BENCH_BACKEND", "nccl") + (" (forced, 1 rank)" if world == 1 else "")) if use_dist else None,
+                       **{k: v for k, v in info.items() if k != "n_train"}},
+            "stage_ms": {"ensemble_infer_plus_im": round(t_inf, 2), "train_epoch": round(t_ep, 2)},
+        }
+    if not args.full:        # a plain run ends with its headline; what follows measures and checks beyond it, mostly in passes of its own
+        prof.close()
+        return out
     if primary and not args.no_prof:
         # which kernel variants make up which stage (launches and algorithmic bytes per generation): one more generation, outside
         # the clock, with the library's totals read at the stage boundary (host-side sums: no synchronisation involved)
@@ -885,18 +935,6 @@ def run_config(args, config_name, alpha, env, primary):
             student.adamw_step(0.0, 0.0, grad_scale=scale)
         host_enqueue.append((time.perf_counter() - t_host) / 8)
     torch.cuda.synchronize()
-    t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-    if use_dist:
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-    elapsed = float(t.item())
-    t_inf = sum(a.elapsed_time(b) for a, b, _ in rec) / len(rec)
-    t_ep = sum(b.elapsed_time(c) for _, b, c in rec) / len(rec)
-    totals = torch.cat([totals, torch.tensor([float(info.pop("n_train"))], dtype=torch.float64, device=dev)])
-    if use_dist:
-        dist.all_reduce(totals)
-    n_all = U_total * (1 if strong else world)
-    info.update(kept=int(totals[2]), train_images=int(totals[3]), mean_pred_size=round(float(totals[0]) / n_all, 1),
-                mean_im_size=round(float(totals[1]) / n_all, 1))
 
     # ---- sharding changes nothing: the whole set on one rank gives the ranks' summed sizes and kept count --------------
     sharding_check = None
@@ -1161,30 +1199,8 @@ def run_config(args, config_name, alpha, env, primary):
                  "frac_of_hbm_peak": round(im_bytes / im_ms / 1e6 / HBM_PEAK_GBS, 4),
                  "bytes_per_launch": im_bytes, "ms_per_launch": round(im_ms, 4)}
 
-    out = None
     if rank == 0:
-        n_images = U_total if strong else U_total * world
-        out = {
-            "metric": "images/sec per IM generation (ensemble infer + IM build + 1 train epoch), 256x256" if (H, W) == (256, 256)
-                      else f"images/sec per IM generation (ensemble infer + IM build + 1 train epoch), {H}x{W}",
-            "value": round(n_images * args.steps / elapsed, 2), "unit": "images/s", "n_gpus": n_gpus,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1000 * elapsed / args.steps, 2),
-            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "f16",
-            "data": "synthetic",
-            "config": {"workload": cfg["workload"], "name": config_name, "alpha": ALPHA, "shape": [H, W, C], "outputs": K,
-                       "unlabeled_images": n_images, "unlabeled_images_per_gpu": U,
-                       "labeled_images": L_total if strong else L_total * world,
-                       "n_models": N_MODELS, "infer_batch": infer_batch,
-                       "infer_batch_rule": "functions.infer_batch_size: 584 at alpha<=0.5 else 128; short tail spread" if not args.infer_batch else "--infer-batch",
-                       "train_batch_per_gpu": BATCH,
-                       "global_batch": BATCH * world, "parallelism": f"dp{world}",
-                       "bn_momentum": {"rule": bn_rule, "value": round(bn_mom, 6)},
-                       "process_group": (os.environ.get("IMK_BENCH_BACKEND", "nccl") + (" (forced, 1 rank)" if world == 1 else "")) if use_dist else None,
-                       **{k: v for k, v in info.items() if k != "n_train"}},
-            "stage_ms": {"ensemble_infer_plus_im": round(t_inf, 2), "train_epoch": round(t_ep, 2)},
-            "roofline": roofline,
-            "im_kernel": im_kernel,
-        }
+        out.update(roofline=roofline, im_kernel=im_kernel)
         if kernel_totals:
             out["timed_region_kernel_totals"] = {k: {"launches": t["launches"], "MB_per_launch": round(t["bytes"] / max(t["launches"], 1) / 1e6, 3),
                                                      "GFLOP_per_launch": round(t["flops"] / max(t["launches"], 1) / 1e9, 4)}

@@ -19,34 +19,34 @@ if [ "$ONLY" = "pmc" ]; then      # HBM traffic passes for the other configurati
 for CFG in suim cityscapes hela; do
   mkdir -p $OUT/cfg_$CFG
   for C in FETCH_SIZE WRITE_SIZE; do
-    rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/cfg_$CFG/pmc_$C -- python3 $R/bench.py --config $CFG --steps 1 --no-cpu-baseline --no-prof > /dev/null 2> $OUT/cfg_$CFG/pmc_$C.err
+    rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/cfg_$CFG/pmc_$C -- python3 $R/bench.py --full --config $CFG --steps 1 --no-cpu-baseline --no-prof > /dev/null 2> $OUT/cfg_$CFG/pmc_$C.err
   done
   python3 $R/profiles/summarize.py $OUT/cfg_$CFG
 done
 exit 0
 fi
 # 1. the default bench command (BASELINE configs[1]), plain and under the kernel trace (+stats)
-python3 $R/bench.py > $OUT/bench.json 2> $OUT/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --no-cpu-baseline > $OUT/bench_traced.json 2> $OUT/trace.err
+python3 $R/bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --full --no-cpu-baseline > $OUT/bench_traced.json 2> $OUT/trace.err
 # 2. HBM traffic of every kernel: FETCH_SIZE and WRITE_SIZE in separate passes of the same command
 for C in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/pmc_$C -- python3 $R/bench.py --no-cpu-baseline --no-prof > $OUT/pmc_$C.json 2> $OUT/pmc_$C.err
+  rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/pmc_$C -- python3 $R/bench.py --full --no-cpu-baseline --no-prof > $OUT/pmc_$C.json 2> $OUT/pmc_$C.err
 done
 python3 $R/profiles/summarize.py $OUT
 # 3. the other BASELINE shapes: bench lines (with their CPU baselines), kernel stats, and the counters for Cityscapes
 for CFG in suim cityscapes hela; do
-  python3 $R/bench.py --config $CFG --steps 2 > $OUT/bench_$CFG.json 2> $OUT/bench_$CFG.err
+  python3 $R/bench.py --full --config $CFG --steps 2 > $OUT/bench_$CFG.json 2> $OUT/bench_$CFG.err
 done
-python3 $R/bench.py --config cityscapes --alpha 2 --steps 2 --no-cpu-baseline > $OUT/bench_cityscapes_a2.json 2> $OUT/bench_cityscapes_a2.err
+python3 $R/bench.py --full --config cityscapes --alpha 2 --steps 2 --no-cpu-baseline > $OUT/bench_cityscapes_a2.json 2> $OUT/bench_cityscapes_a2.err
 for CFG in suim cityscapes hela; do
   mkdir -p $OUT/cfg_$CFG
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/cfg_$CFG/trace -- python3 $R/bench.py --config $CFG --steps 1 --no-cpu-baseline > /dev/null 2> $OUT/cfg_$CFG/trace.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/cfg_$CFG/trace -- python3 $R/bench.py --full --config $CFG --steps 1 --no-cpu-baseline > /dev/null 2> $OUT/cfg_$CFG/trace.err
   python3 $R/profiles/summarize.py $OUT/cfg_$CFG
 done
 mkdir -p $OUT/cfg_cityscapes_a2
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/cfg_cityscapes_a2/trace -- python3 $R/bench.py --config cityscapes --alpha 2 --steps 1 --no-cpu-baseline > /dev/null 2> $OUT/cfg_cityscapes_a2/trace.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/cfg_cityscapes_a2/trace -- python3 $R/bench.py --full --config cityscapes --alpha 2 --steps 1 --no-cpu-baseline > /dev/null 2> $OUT/cfg_cityscapes_a2/trace.err
 for C in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/cfg_cityscapes_a2/pmc_$C -- python3 $R/bench.py --config cityscapes --alpha 2 --steps 1 --no-cpu-baseline --no-prof > /dev/null 2> $OUT/cfg_cityscapes_a2/pmc_$C.err
+  rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/cfg_cityscapes_a2/pmc_$C -- python3 $R/bench.py --full --config cityscapes --alpha 2 --steps 1 --no-cpu-baseline --no-prof > /dev/null 2> $OUT/cfg_cityscapes_a2/pmc_$C.err
 done
 python3 $R/profiles/summarize.py $OUT/cfg_cityscapes_a2
 # 4. kernel-by-kernel timelines of one training step and one inference call

@@ -20,25 +20,25 @@ cd /tmp
 if [ "$ONLY" = "times" ]; then step_times; exit 0; fi
 # 1. the default bench command (BASELINE configs[1] + other_configs), plain and under the kernel trace (+stats): the traced run's
 #    line carries the library's per-kernel byte totals of the timed region, the trace its marker dispatches
-python3 $R/bench.py > $OUT/bench.json 2> $OUT/bench.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --no-cpu-baseline --no-other-configs > $OUT/bench_traced.json 2> $OUT/trace.err
+python3 $R/bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $R/bench.py --full --no-cpu-baseline --no-other-configs > $OUT/bench_traced.json 2> $OUT/trace.err
 # 2. HBM traffic of every kernel: FETCH_SIZE and WRITE_SIZE in separate passes of the same command
 for C in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/pmc_$C -- python3 $R/bench.py --no-cpu-baseline --no-other-configs --no-prof > $OUT/pmc_$C.json 2> $OUT/pmc_$C.err
+  rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/pmc_$C -- python3 $R/bench.py --full --no-cpu-baseline --no-other-configs --no-prof > $OUT/pmc_$C.json 2> $OUT/pmc_$C.err
 done
 python3 $R/profiles/summarize.py $OUT
 if [ "$ONLY" = "bench" ]; then du -sh $OUT; exit 0; fi
 # 3. the other BASELINE shapes: bench lines (with their CPU baselines), kernel stats and HBM traffic
 for CFG in suim cityscapes hela; do
-  python3 $R/bench.py --config $CFG --steps 2 > $OUT/bench_$CFG.json 2> $OUT/bench_$CFG.err
+  python3 $R/bench.py --full --config $CFG --steps 2 > $OUT/bench_$CFG.json 2> $OUT/bench_$CFG.err
 done
-python3 $R/bench.py --config cityscapes --alpha 2 --steps 2 --no-cpu-baseline > $OUT/bench_cityscapes_a2.json 2> $OUT/bench_cityscapes_a2.err
+python3 $R/bench.py --full --config cityscapes --alpha 2 --steps 2 --no-cpu-baseline > $OUT/bench_cityscapes_a2.json 2> $OUT/bench_cityscapes_a2.err
 for CFG in suim cityscapes hela cityscapes_a2; do
   A=""; N=$CFG; [ "$CFG" = "cityscapes_a2" ] && { A="--alpha 2"; N=cityscapes; }
   mkdir -p $OUT/cfg_$CFG
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/cfg_$CFG/trace -- python3 $R/bench.py --config $N $A --steps 1 --no-cpu-baseline > $OUT/cfg_$CFG/bench_traced.json 2> $OUT/cfg_$CFG/trace.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/cfg_$CFG/trace -- python3 $R/bench.py --full --config $N $A --steps 1 --no-cpu-baseline > $OUT/cfg_$CFG/bench_traced.json 2> $OUT/cfg_$CFG/trace.err
   for C in FETCH_SIZE WRITE_SIZE; do
-    rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/cfg_$CFG/pmc_$C -- python3 $R/bench.py --config $N $A --steps 1 --no-cpu-baseline --no-prof > /dev/null 2> $OUT/cfg_$CFG/pmc_$C.err
+    rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/cfg_$CFG/pmc_$C -- python3 $R/bench.py --full --config $N $A --steps 1 --no-cpu-baseline --no-prof > /dev/null 2> $OUT/cfg_$CFG/pmc_$C.err
   done
   python3 $R/profiles/summarize.py $OUT/cfg_$CFG
 done

@@ -40,13 +40,13 @@ for CFG in $CONFIGS; do
   python3 $R/bench.py --provenance > $D/provenance.json
   # 1. the plain command (the default one carries the CPU baseline and other_configs), then the same under the kernel trace (+stats):
   #    the traced run's full record holds the library's per-kernel byte totals of the timed region, the trace its marker dispatches
-  python3 $R/bench.py $ARGS $PLAIN --detail $D/bench_detail.json > $D/bench.json 2> $D/bench.err
+  python3 $R/bench.py --full $ARGS $PLAIN --detail $D/bench_detail.json > $D/bench.json 2> $D/bench.err
   TR="--no-cpu-baseline --no-other-configs"; [ -n "$TAG" ] && TR="--no-cpu-baseline --steps 1"
-  rocprofv3 --kernel-trace --stats --output-format csv -d $D/trace -- python3 $R/bench.py $ARGS $TR --detail $D/bench_traced_detail.json > $D/bench_traced.json 2> $D/trace.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $D/trace -- python3 $R/bench.py --full $ARGS $TR --detail $D/bench_traced_detail.json > $D/bench_traced.json 2> $D/trace.err
   # 2. HBM traffic of every kernel: FETCH_SIZE and WRITE_SIZE in separate passes of the same command
   if [ "$PMC" = "1" ]; then
     for C in FETCH_SIZE WRITE_SIZE; do
-      rocprofv3 --kernel-trace --pmc $C --output-format csv -d $D/pmc_$C -- python3 $R/bench.py $ARGS $TR --no-prof --detail $D/pmc_${C}_detail.json > /dev/null 2> $D/pmc_$C.err
+      rocprofv3 --kernel-trace --pmc $C --output-format csv -d $D/pmc_$C -- python3 $R/bench.py --full $ARGS $TR --no-prof --detail $D/pmc_${C}_detail.json > /dev/null 2> $D/pmc_$C.err
     done
   fi
   python3 $R/profiles/summarize.py $D

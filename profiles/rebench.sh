@@ -13,6 +13,6 @@ for CFG in isic suim cityscapes hela cityscapes_a2 cityscapes_a125; do
     cityscapes_a125) ARGS="--config cityscapes --alpha 1.25 --steps 2 --no-cpu-baseline"; TAG="_cityscapes_a125" ;;
   esac
   D=$OUT/cfg$TAG; mkdir -p $D
-  python3 $R/bench.py $ARGS --detail $D/bench_detail.json > $D/bench.json 2> $D/bench.err
+  python3 $R/bench.py --full $ARGS --detail $D/bench_detail.json > $D/bench.json 2> $D/bench.err
   tail -c 300 $D/bench.json; echo
 done

@@ -793,7 +793,7 @@ def test_bench_one_rank_process_group_rccl():
     import json
     env = {**os.environ, "IMK_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1"}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--images", "96", "--labeled", "32", "--steps", "1",
-                        "--pretrain-steps", "10", "--bn-settle-steps", "10", "--no-cpu-baseline"], env=env, capture_output=True,
+                        "--pretrain-steps", "10", "--bn-settle-steps", "10", "--no-cpu-baseline", "--full"], env=env, capture_output=True,
                        text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     from test_cpu_api import check_bench_line
@@ -817,6 +817,7 @@ def test_bench_dump_outputs(tmp_path):
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     out = json.loads(r.stdout.strip().splitlines()[-1])
     assert out["steps"] == 2 and out["ms_per_step"] > 0
+    assert not {"roofline", "im_kernel", "cpu_baseline", "detail"} & set(out)       # a plain run: the headline only, no --full passes
     d = {f[:-4]: np.load(out_dir / f) for f in os.listdir(out_dir)}
     assert all(a.dtype in (np.float32, np.float64) for a in d.values()) and sum(a.nbytes for a in d.values()) <= 64 << 20
     assert d["pred_size"].shape == d["im_size"].shape == (96, 1) and d["keep"].shape == (96,)
@@ -889,7 +890,7 @@ def test_bench_eight_ranks_full_set_on_one_gpu():
     env = {**os.environ, "IMK_BENCH_ONE_GPU": "1", "IMK_BENCH_BACKEND": "gloo"}
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "8", "--images", "2335", "--labeled", "259", "--steps", "1",
-           "--warmup", "0", "--pretrain-steps", "10", "--bn-settle-steps", "10", "--no-cpu-baseline", "--no-prof"]
+           "--warmup", "0", "--pretrain-steps", "10", "--bn-settle-steps", "10", "--no-cpu-baseline", "--no-prof", "--full"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1700)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
