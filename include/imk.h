@@ -271,6 +271,59 @@ IMK_API int imk_augment(const uint8_t *img, const uint8_t *mask, int batch, int 
                 const imk_aug_params *params, uint8_t *img_out, uint8_t *mask_out, int any_quarter_turn, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Input-ensemble baseline: one model voting with itself over augmented views of each image
+ * (get_input_ensemble_prediction_*, functions.py:1409-1459, 1570-1764, 2127-2407)
+ * ---------------------------------------------------------------------------------------------- */
+#define IMK_VIEWS_MAX 16          /* views per image the fused and unfused view votes take (the 13-view form fits) */
+typedef struct imk_view_params {  /* one per (view, image), device array [M][B] */
+    int op;                       /* D4 op: 0 identity, 1..12 = 1 + 6 fh + 3 fv + (rot - 1), the order of
+                                     generate_random_transformations (functions.py:1675-1726): fh = cv2.flip(., 0),
+                                     fv = cv2.flip(., 1), rot 1 = 90 CW, 2 = 180, 3 = 90 CCW, applied in that order */
+    int blur_k;                   /* 0/1 none, 3, 5, 7: GaussianBlur((k,k), 0)        (functions.py:1494-1501) */
+    int noise_max;                /* uniform integer noise in [-m, m), then clip      (functions.py:1463-1478) */
+    uint32_t seed;                /* seed of the counter-based noise generator (imk_augment's) */
+    int bright_on;                /* convertScaleAbs(alpha, beta)                     (functions.py:1589-1593) */
+    float alpha, beta;
+} imk_view_params;
+
+/* M views per image: img [B,H,W,C] u8 -> views_out [M,B,H,W,C] u8 (member-major), each
+ * geometry(op) -> blur -> noise -> brightness (data_augmentation_image, functions.py:1570-1594), with imk_augment's pixel
+ * arithmetic.  chain = 0: every view is made from the image (ISIC); chain = 1: view m is made from view m-1 and view 0 from the
+ * image (the HeLa / multi-class loops), as M dependent launches.  Quarter turns need h == w (set any_quarter_turn if any op is
+ * a quarter turn), else IMK_EUNSUPPORTED.  Not in place. */
+IMK_API int imk_views(const uint8_t *img, int batch, int h, int w, int c, int n_views, const imk_view_params *params,
+                      int chain, int any_quarter_turn, uint8_t *views_out, void *stream);
+
+/* The D4-restoring hard vote on an fp32 stack.  preds [M,B,H,W,K] float32 (views of image b at rows m*B + b), ops device int32
+ * [M,B] (NULL: identity) -> masks_out [B,K,H,W] {0,255}: 255 where every view, read at the pixel its op moved (y, x) to, has
+ * p >= (float)thr (cmp_ge = 1, the ISIC rule) or p > (float)thr (cmp_ge = 0).  NaN votes 0.  Quarter turns need h == w. */
+IMK_API int imk_vote_views_binary(const float *preds, int n_views, int batch, int h, int w, int k, const int *ops,
+                                  int any_quarter_turn, double thr, int cmp_ge, uint8_t *masks_out, void *stream);
+
+/* The majority of the per-view arg-maxes (get_input_ensemble_prediction_multiclass, functions.py:2182-2218): np.argmax per view
+ * (the first maximum; the first NaN wins), then np.argmax(np.bincount(.)), so ties go to the smallest label.
+ * probs [M,B,H,W,K] float32, M <= IMK_VIEWS_MAX -> final_out [B,H,W] u8. */
+IMK_API int imk_vote_views_majority(const float *probs, int n_views, int batch, int h, int w, int k, uint8_t *final_out,
+                                    void *stream);
+
+enum { IMK_VOTE_MAJORITY = 2 };
+/* One model's forward over the B*M views [M,B,H,W,C] as one batch, then the input-ensemble vote -> masks_out:
+ *   sigmoid head, ops != NULL:  the D4-restoring hard vote of imk_vote_views_binary (mode IMK_VOTE_HARD), fused with the head
+ *                               for M <= IMK_VIEWS_MAX, K <= 4 and last decoder widths 8/16/24/32;
+ *   sigmoid head, ops == NULL:  imk_vote_binary's rules (mode IMK_VOTE_HARD: p > thr; IMK_VOTE_SOFT: the fp64 mean), fused
+ *                               through the model-ensemble head kernel with every member's weights the same;
+ *   softmax head:               IMK_VOTE_SOFT (argmax of the fp32 mean, fused likewise) or IMK_VOTE_MAJORITY.
+ * Outputs are bit-identical to imk_unet_forward over the views + imk_vote_views_binary / imk_vote_binary / imk_vote_multiclass /
+ * imk_vote_views_majority, which is the route for the shapes the fused kernels do not cover: there the forwards run per view
+ * and image chunk so that the fp32 stack of the whole batch is never held.  The workspace is sized by
+ * imk_unet_forward_views_vote_workspace_bytes(plan, M, B). */
+IMK_API int64_t imk_unet_forward_views_vote_workspace_bytes(const imk_unet_plan *plan, int n_views, int batch);
+IMK_API int imk_unet_forward_views_vote(const imk_unet_plan *plan, const float *params, const void *packed,
+                                        const uint8_t *views, int n_views, int batch, const int *ops, int any_quarter_turn,
+                                        double thr, int mode, int cmp_ge, uint8_t *masks_out, void *workspace,
+                                        int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Evaluation reductions (benchmark_ISIC2018 / benchmark_multiclass)
  * ---------------------------------------------------------------------------------------------- */
 /* Replaces the threshold + per-image numpy metric loop of benchmark_ISIC2018 (functions.py:1120-1140) with

@@ -24,6 +24,11 @@ class AugParams(ctypes.Structure):
                 ("beta", c_float), ("blur_k", c_int), ("noise_max", c_int), ("seed", ctypes.c_uint32)]
 
 
+class ViewParams(ctypes.Structure):
+    _fields_ = [("op", c_int), ("blur_k", c_int), ("noise_max", c_int), ("seed", ctypes.c_uint32), ("bright_on", c_int),
+                ("alpha", c_float), ("beta", c_float)]
+
+
 class LayerInfo(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 16), ("kind", c_int), ("ksize", c_int), ("cin", c_int), ("cout", c_int),
                 ("off_w", c_int64), ("off_b", c_int64), ("off_mean", c_int64), ("off_var", c_int64)]
@@ -62,6 +67,13 @@ SIGNATURES = {
     "imk_vote_multiclass": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "imk_unet_forward_vote": (c_int, [c_void_p, c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
                                       c_void_p, c_int, ctypes.c_double, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "imk_views": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "imk_vote_views_binary": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, ctypes.c_double, c_int,
+                                      c_void_p, c_void_p]),
+    "imk_vote_views_majority": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "imk_unet_forward_views_vote_workspace_bytes": (c_int64, [c_void_p, c_int, c_int]),
+    "imk_unet_forward_views_vote": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
+                                            ctypes.c_double, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "imk_unet_state_bytes": (c_int64, [c_void_p]),
     "imk_unet_state_init": (c_int, [c_void_p, c_void_p, c_void_p]),
     "imk_unet_fwd_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,

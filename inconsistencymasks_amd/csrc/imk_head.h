@@ -200,3 +200,18 @@ struct ImkVoteHeadArgs {
 // Sigmoid heads in the shapes of imk_head_im_supported; the caller takes imk_unet_forward + imk_vote_* otherwise.
 bool imk_vote_head_supported(const ImkVoteHeadArgs &a);
 int imk_launch_vote_head(const ImkVoteHeadArgs &a, hipStream_t stream);
+
+// ---- fused head + D4-restoring input-ensemble vote (imk_views.hip) --------------------------------------------------------
+struct ImkViewVoteArgs {
+    const f16 *z;                                // last decoder block's conv output of the M*B views [M,B,H,W,cs]
+    const float *sc, *sh, *wt, *bias;            // its folded BatchNorm; the head's fp32 kernel [cin][K] / bias [K] (one model)
+    const int *ops;                              // device [M][ops_ld]: the D4 op of view m of image b at m * ops_ld + b
+    int ops_ld, n_views, cin, cs, K, batch, h, w;
+    double thr;                                  // compared as (float)thr
+    int cmp_ge;                                  // p >= thr (ISIC) or p > thr
+    uint8_t *out;                                // masks [B,K,H,W] {0,255}
+};
+bool imk_views_vote_head_supported(const ImkViewVoteArgs &a);
+int imk_launch_views_vote_head(const ImkViewVoteArgs &a, hipStream_t stream);
+int imk_vote_views_binary_ld(const float *preds, int n_views, int batch, int h, int w, int k, const int *ops, int ops_ld,
+                             double thr, int cmp_ge, uint8_t *masks_out, hipStream_t stream);

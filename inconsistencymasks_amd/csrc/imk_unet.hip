@@ -441,6 +441,96 @@ extern "C" int imk_unet_forward_vote(const imk_unet_plan *plan, int n_models, co
     return imk_vote_multiclass((const float *)base, n_models, batch, cf.h, cf.w, cf.n_out, mode, masks_out, stream_);
 }
 
+// Input ensemble: one model's forward over the B*M views as one batch.  Fused: the last decoder activation of the whole batch goes
+// to a head slab and one vote kernel reads it -- the D4-restoring kernel (imk_views.hip) for ops != NULL, the model-ensemble head
+// kernel (imk_vote.hip) with member m = slice m of the slab and the same weights for every member otherwise.  Unfused: per image
+// chunk, one forward per view into an fp32 stack [M,bc,H,W,K], then the stack vote; bc is the largest chunk whose stack and
+// activation workspace fit the fused route's workspace.
+extern "C" int64_t imk_unet_forward_views_vote_workspace_bytes(const imk_unet_plan *plan, int n_views, int batch) {
+    if (!plan || plan->net != 0 || n_views <= 0 || batch <= 0) return IMK_EINVAL;
+    const int mb = n_views * batch;
+    return (int64_t)(head_slab_bytes(plan, mb, true) + make_ws(plan, mb, 0).total);
+}
+
+extern "C" int imk_unet_forward_views_vote(const imk_unet_plan *plan, const float *params, const void *packed,
+                                           const uint8_t *views, int n_views, int batch, const int *ops, int any_quarter_turn,
+                                           double thr, int mode, int cmp_ge, uint8_t *masks_out, void *workspace,
+                                           int64_t workspace_bytes, void *stream_) {
+    IMK_CHECK_ARG(plan && plan->net == 0 && params && packed && views && masks_out && workspace && batch > 0 && n_views > 0);
+    const imk_unet_cfg &cf = plan->cfg;
+    const bool sigmoid = cf.act_out == 0;
+    IMK_CHECK_ARG(mode == IMK_VOTE_HARD || mode == IMK_VOTE_SOFT || (!sigmoid && mode == IMK_VOTE_MAJORITY));
+    IMK_CHECK_ARG(!ops || (sigmoid && mode == IMK_VOTE_HARD));
+    if (ops && any_quarter_turn && cf.h != cf.w) return IMK_EUNSUPPORTED;
+    const int mb = n_views * batch;
+    IMK_CHECK_ARG(mb <= 65535);
+    const Topo topo = make_topo(plan);
+    const ImkLayer &o = plan->layers[topo.out];
+    hipStream_t stream = (hipStream_t)stream_;
+    uint8_t *base = (uint8_t *)workspace;
+    const int hw = cf.h * cf.w, cs = imk_pad8(cf.ch[0]);
+    ImkViewVoteArgs da{};     // D4-restoring (ops)
+    da.ops = ops; da.ops_ld = batch; da.n_views = n_views; da.cin = cf.ch[0]; da.cs = cs; da.K = cf.n_out; da.batch = batch;
+    da.h = cf.h; da.w = cf.w; da.thr = thr; da.cmp_ge = cmp_ge; da.out = masks_out;
+    ImkVoteHeadArgs va{};     // identity maps
+    va.n_models = n_views; va.cin = cf.ch[0]; va.cs = cs; va.K = cf.n_out; va.softmax = cf.act_out; va.batch = batch; va.hw = hw;
+    va.thr = thr; va.mode = mode; va.out = masks_out;
+    const bool kernel_ok = ops ? imk_views_vote_head_supported(da)
+                               : (mode != IMK_VOTE_MAJORITY && !(sigmoid && cmp_ge) && imk_vote_head_supported(va));
+    const Ws ws = make_ws(plan, mb, 0);
+    const size_t slab = head_slab_bytes(plan, mb, true);
+    if (!plan->dbg_materialize && kernel_ok && (int64_t)(slab + ws.total) <= workspace_bytes) {
+        Ctx c{plan, ws, base + slab, params, (const uint8_t *)packed, mb, false, stream};
+        c.x_in[0] = views;
+        c.ovr_conv = topo.d_c1[3];
+        c.ovr_out = reinterpret_cast<f16 *>(base);
+        const float *sc = c.bn_scale(topo.d_bnb[3]), *sh = c.bn_shift(topo.d_bnb[3]);
+        int rc = run_forward(c, topo, nullptr, nullptr);
+        if (rc) return rc;
+        if (ops) {
+            da.z = c.ovr_out; da.sc = sc; da.sh = sh; da.wt = params + o.off_w; da.bias = params + o.off_b;
+            return imk_launch_views_vote_head(da, stream);
+        }
+        for (int m = 0; m < n_views; ++m) {
+            va.z[m] = c.ovr_out + (size_t)m * batch * hw * cs;
+            va.sc[m] = sc; va.sh[m] = sh; va.w[m] = params + o.off_w; va.bias[m] = params + o.off_b;
+        }
+        return imk_launch_vote_head(va, stream);
+    }
+    // unfused: image chunks of bc, the stack [M,bc,H,W,K] at the start of the workspace
+    const size_t img_probs = (size_t)hw * cf.n_out * sizeof(float);
+    int bc = batch;
+    while (bc > 0 && (int64_t)(up(img_probs * n_views * bc) + make_ws(plan, bc, 0).total) > workspace_bytes) bc = bc > 8 ? bc * 3 / 4 : bc - 1;
+    if (bc <= 0) return IMK_EWORKSPACE;
+    float *stack = (float *)base;
+    const size_t hwc = (size_t)hw * cf.c_in;
+    for (int b0 = 0; b0 < batch; b0 += bc) {
+        const int n = batch - b0 < bc ? batch - b0 : bc;
+        const Ws wsc = make_ws(plan, n, 0);
+        for (int m = 0; m < n_views; ++m) {
+            Ctx c{plan, wsc, base + up(img_probs * n_views * bc), params, (const uint8_t *)packed, n, false, stream};
+            c.x_in[0] = views + ((size_t)m * batch + b0) * hwc;
+            int rc = run_forward(c, topo, stack + (size_t)m * n * hw * cf.n_out, nullptr);
+            if (rc) return rc;
+        }
+        int rc;
+        if (ops)
+            rc = imk_vote_views_binary_ld(stack, n_views, n, cf.h, cf.w, cf.n_out, ops + b0, batch, thr, cmp_ge,
+                                          masks_out + (size_t)b0 * cf.n_out * hw, stream);
+        else if (sigmoid && cmp_ge && mode == IMK_VOTE_HARD)
+            rc = imk_vote_views_binary_ld(stack, n_views, n, cf.h, cf.w, cf.n_out, nullptr, 0, thr, 1,
+                                          masks_out + (size_t)b0 * cf.n_out * hw, stream);
+        else if (sigmoid)
+            rc = imk_vote_binary(stack, n_views, n, cf.h, cf.w, cf.n_out, thr, mode, masks_out + (size_t)b0 * cf.n_out * hw, stream_);
+        else if (mode == IMK_VOTE_MAJORITY)
+            rc = imk_vote_views_majority(stack, n_views, n, cf.h, cf.w, cf.n_out, masks_out + (size_t)b0 * hw, stream_);
+        else
+            rc = imk_vote_multiclass(stack, n_views, n, cf.h, cf.w, cf.n_out, mode, masks_out + (size_t)b0 * hw, stream_);
+        if (rc) return rc;
+    }
+    return IMK_OK;
+}
+
 // =====================================================================================================
 // training
 // =====================================================================================================

@@ -15,7 +15,9 @@ mean IM size) and `train_*` averages gradients with one all-reduce per step (RCC
 import configparser
 import glob
 import os
+import random as _random
 import re
+import zlib
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -24,6 +26,7 @@ from PIL import Image
 
 from . import evaluate as _ev
 from . import im as _im
+from . import input_ensemble as _ie
 from . import vote as _vote
 from ._lib import check, lib
 from .unet import UNet, _stream
@@ -1525,6 +1528,150 @@ def create_pseudo_labels_model_ensemble_hela(models, bf_images_path, main_output
         return [(os.path.join(out["brightfield"], name), img), (os.path.join(out["alive"], name), m[0]),
                 (os.path.join(out["dead"], name), m[1]), (os.path.join(out["mod_position"], name), _hela_vote_positions(m[2], 8, 3))]
     _run_vote_writer(models, bf_images_path, c, True, True, 0.5, False, per_image)
+
+
+# ---------------------------------------------------------------------------------------------------
+# Input-ensemble baseline (functions.py:1409-1459, 1570-1764, 2127-2407): one model voting with itself over augmented views of
+# the image.  The views come from imk_views, the vote from imk_unet_forward_views_vote (native UNet) or the stack votes on the
+# predictions of duck-typed `.predict` models (input_ensemble.py).  The Python `random` draws are the reference's, in its order
+# (ops, blur sizes, coins); the noise and alpha / beta cannot match its numpy stream (input_ensemble.py says why).
+# ---------------------------------------------------------------------------------------------------
+def _image_batch(image, h, w, c):
+    return torch.as_tensor(np.ascontiguousarray(np.asarray(image, dtype=np.uint8).reshape(1, h, w, c))).cuda()
+
+
+def data_augmentation_image(image, max_blur, max_noise, brightness_range_alpha, brightness_range_beta):
+    """functions.py:1570-1594 for one [H,W] or [H,W,C] uint8 image: blur (random.randint(0, max_blur)), noise in [-m, m), then,
+    if random.randint(0, 1) is 1, convertScaleAbs with alpha / beta drawn from np.random.  The noise is imk_views' counter-hash
+    field (its seed drawn from np.random), not numpy's draw."""
+    a = np.asarray(image, dtype=np.uint8)
+    h, w = a.shape[:2]
+    c = a.shape[2] if a.ndim == 3 else 1
+    q = _ie.draw_chain_views(0, max_blur, max_noise, brightness_range_alpha, brightness_range_beta)
+    v = _ie.make_views(_image_batch(a, h, w, c), _ie.ViewPlan([q]))
+    return v[0, 0].cpu().numpy().reshape(a.shape)
+
+
+def get_input_ensemble_prediction_ISIC_2018(model, image, h, w, c, threshold, n=2, max_blur=3, max_noise=25,
+                                            brightness_range_alpha=(0.5, 1.5), brightness_range_beta=(-25, 25),
+                                            use_n_rnd_transformations=True):
+    """functions.py:2127-2180: n random views (or the 13 of the identity and the 12 combinations), each restored, 255 where every
+    view has p >= threshold.  uint8 [H, W]."""
+    views = _ie.draw_random_views(n, max_blur, max_noise, brightness_range_alpha, brightness_range_beta) \
+        if use_n_rnd_transformations else _ie.all_views()
+    plan = _ie.ViewPlan([views], restore=True)
+    return _ie.ViewVote(model, True).run(_image_batch(image, h, w, c), plan, threshold, _vote.VOTE_HARD, True)[0, 0].cpu().numpy()
+
+
+def input_ensemble_prediction(model, image, h, w, c, threshold, max_blur=3, max_noise=25, brightness_range_alpha=(0.5, 1.5),
+                              brightness_range_beta=(-25, 25), n=2, use_n_rnd_transformations=False):
+    """functions.py:1409-1459: get_input_ensemble_prediction_ISIC_2018 with the 13 views by default."""
+    return get_input_ensemble_prediction_ISIC_2018(model, image, h, w, c, threshold, n, max_blur, max_noise, brightness_range_alpha,
+                                                   brightness_range_beta, use_n_rnd_transformations)
+
+
+def _chain_vote(model, image, h, w, c, n, max_blur, max_noise, brightness_range_alpha, brightness_range_beta, binary, thr, mode):
+    views = _ie.draw_chain_views(n, max_blur, max_noise, brightness_range_alpha, brightness_range_beta)
+    return _ie.ViewVote(model, binary).run(_image_batch(image, h, w, c), _ie.ViewPlan([views], chain=True), thr, mode, False)[0]
+
+
+def get_input_ensemble_prediction_hela_hard(model, image, h, w, c, n=2, max_blur=1, max_noise=15, brightness_range_alpha=(0.7, 1.3),
+                                            brightness_range_beta=(-15, 15), threshold=0.5, max_pos_circle_size=8,
+                                            min_pos_circle_size=3):
+    """functions.py:2295-2363: n + 1 chained views, 255 where all have p > threshold per channel, then the position circles.
+    Returns (alive [H,W] u8, dead [H,W] u8, pos [H,W,3] u8)."""
+    m = _chain_vote(model, image, h, w, c, n, max_blur, max_noise, brightness_range_alpha, brightness_range_beta, True, threshold,
+                    _vote.VOTE_HARD).cpu().numpy()
+    return m[0], m[1], _hela_vote_positions(m[2], max_pos_circle_size, min_pos_circle_size)
+
+
+def get_input_ensemble_prediction_hela_soft(model, image, h, w, c, n=2, max_blur=1, max_noise=15, brightness_range_alpha=(0.7, 1.3),
+                                            brightness_range_beta=(-15, 15), threshold=0.5, max_pos_circle_size=8,
+                                            min_pos_circle_size=3):
+    """functions.py:2221-2293: n + 1 chained views, the fp64 mean > threshold per channel, then the position circles."""
+    m = _chain_vote(model, image, h, w, c, n, max_blur, max_noise, brightness_range_alpha, brightness_range_beta, True, threshold,
+                    _vote.VOTE_SOFT).cpu().numpy()
+    return m[0], m[1], _hela_vote_positions(m[2], max_pos_circle_size, min_pos_circle_size)
+
+
+def get_input_ensemble_prediction_multiclass_soft(model, image, h, w, c, n=2, max_blur=1, max_noise=15,
+                                                  brightness_range_alpha=(0.7, 1.3), brightness_range_beta=(-15, 15)):
+    """functions.py:2365-2407: argmax of the fp32 mean over the n + 1 chained views.  uint8 [H, W]."""
+    return _chain_vote(model, image, h, w, c, n, max_blur, max_noise, brightness_range_alpha, brightness_range_beta, False, 0.5,
+                       _vote.VOTE_SOFT).cpu().numpy()
+
+
+def get_input_ensemble_prediction_multiclass(model, image, h, w, c, n=2, max_blur=1, max_noise=15, brightness_range_alpha=(0.7, 1.3),
+                                             brightness_range_beta=(-15, 15)):
+    """functions.py:2182-2218: the most common per-view arg-max over the n + 1 chained views, ties to the smallest label."""
+    return _chain_vote(model, image, h, w, c, n, max_blur, max_noise, brightness_range_alpha, brightness_range_beta, False, 0.5,
+                       _ie.VOTE_MAJORITY).cpu().numpy()
+
+
+def _view_rngs(main_output_path, name):
+    """the draws of one image of a writer: random.Random / numpy RandomState seeded by (SEED, output directory, file name), so the
+    files do not depend on the rank count or the batch size"""
+    key = f"{SEED}|{os.path.basename(os.path.normpath(main_output_path))}|{name}"
+    return _random.Random(key), np.random.RandomState(zlib.crc32(key.encode()))
+
+
+def _run_view_writer(model, images_path, main_output_path, c, binary, threshold, mode, cmp_ge, flip_channels, draw, chain,
+                     restore, per_image):
+    """Shared body of the input-ensemble writers: this rank's shard of the file list in batches of max(1, infer batch // M) images
+    (the workspace of the model-ensemble writers), one view vote per batch, the files of every image from
+    per_image(name, image [H,W,C] as read, label rows) queued on the writer pool."""
+    mine = shard_list(os.listdir(images_path))
+    vv = _ie.ViewVote(model, binary)
+    n_views = len(draw(_random.Random(0), np.random.RandomState(0)))
+    with _pool() as pool:
+        for i, j in infer_batches(len(mine), max(1, infer_batch_size(_models_alpha(model)) // n_views)):
+            chunk = mine[i:j]
+            imgs = read_png_stack(pool, [os.path.join(images_path, n) for n in chunk], c)
+            x = torch.from_numpy(imgs).cuda()
+            if flip_channels:      # rgb=False: the net sees the file's channel order
+                x = x.flip(-1).contiguous()
+            plan = _ie.ViewPlan([draw(*_view_rngs(main_output_path, n)) for n in chunk], chain, restore)
+            lab = vv.run(x, plan, threshold, mode, cmp_ge)
+            keep = None
+            if restore:            # functions.py:2029-2034: written only if the 5x5 erosion of the vote has a nonzero pixel
+                keep = (_im.morph(lab[:, 0].contiguous(), 5, "erode").flatten(1).amax(1) > 0).cpu().numpy()
+            lab = lab.cpu().numpy()
+            jobs = [job for per in pool.map(lambda q: per_image(chunk[q], imgs[q], lab[q]) if keep is None or keep[q] else [],
+                                            range(len(chunk))) for job in per]
+            write_pngs_async(jobs)
+    flush_writes()
+    d = _dist()
+    if d:      # every rank's files are on disk before rank 0 copies the labelled pairs in beside them
+        d.barrier()
+
+
+def create_pseudo_labels_input_ensemble_ISIC_2018(model, images_path, main_output_path, h, w, c, n=2, rgb=True,
+                                                  use_n_rnd_transformations=True, threshold=0.5):
+    """functions.py:1992-2037: images/ (the image as read) and masks/ (the restored vote, p >= threshold in every view), for the
+    images whose vote survives a 5x5 erosion."""
+    out = _vote_out_dirs(main_output_path, ("images", "masks"))
+    draw = (lambda r, nr: _ie.draw_random_views(n, rng=r, np_rng=nr)) if use_n_rnd_transformations else (lambda r, nr: _ie.all_views())
+    _run_view_writer(model, images_path, main_output_path, c, True, threshold, _vote.VOTE_HARD, True, not rgb and c == 3, draw, False,
+                     True, lambda name, img, m: [(os.path.join(out["images"], name), img), (os.path.join(out["masks"], name), m[0])])
+
+
+def create_pseudo_labels_input_ensemble_hela(model, bf_images_path, main_output_path, h, w, c, n=2, use_soft_voting=False):
+    """functions.py:2040-2084: brightfield/ (as read), alive/ and dead/ (the vote of n + 1 chained views), mod_position/ (circles)."""
+    out = _vote_out_dirs(main_output_path, ("brightfield", "alive", "dead", "mod_position"))
+
+    def per_image(name, img, m):
+        return [(os.path.join(out["brightfield"], name), img), (os.path.join(out["alive"], name), m[0]),
+                (os.path.join(out["dead"], name), m[1]), (os.path.join(out["mod_position"], name), _hela_vote_positions(m[2], 8, 3))]
+    _run_view_writer(model, bf_images_path, main_output_path, c, True, 0.5, _vote.VOTE_SOFT if use_soft_voting else _vote.VOTE_HARD,
+                     False, False, lambda r, nr: _ie.draw_chain_views(n, rng=r, np_rng=nr), True, False, per_image)
+
+
+def create_pseudo_labels_input_ensemble_multiclass(model, images_path, main_output_path, h, w, c, n=2, rgb=True):
+    """functions.py:2087-2124: images/ (the image as read) and masks/ (argmax of the mean over n + 1 chained views)."""
+    out = _vote_out_dirs(main_output_path, ("images", "masks"))
+    _run_view_writer(model, images_path, main_output_path, c, False, 0.5, _vote.VOTE_SOFT, False, not rgb and c == 3,
+                     lambda r, nr: _ie.draw_chain_views(n, rng=r, np_rng=nr), True, False,
+                     lambda name, img, m: [(os.path.join(out["images"], name), img), (os.path.join(out["masks"], name), m)])
 
 
 _HELA_GT_COUNTS = {}      # id(position-mask tensor of a cached decoded set) -> (weak reference to it, [(alive, dead)] ground-truth cell counts)

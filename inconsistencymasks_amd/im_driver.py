@@ -16,7 +16,12 @@ labelled set (TRAIN_LABELED_AUG) instead of the plain one; the multi-class scrip
 approach="model_ensemble" is the model-ensemble baseline (ISIC_2018/06_ISIC_2018_model_ensemble.py, HeLa/06_HeLa_model_ensemble.py,
 SUIM/07_SUIM_model_ensemble.py, Cityscapes/06_Cityscapes_model_ensemble.py): the IM loop with the ensemble's vote in place of the
 IM writer (create_pseudo_labels_model_ensemble_*: no im/ directory, no blocking, no mean_im_size CSV), model names without the
-erode / dilate / blocking suffix, and HeLa candidates ranked by mean_cell_count_error_test, ascending (HeLa/06_HeLa_model_ensemble.py:120)."""
+erode / dilate / blocking suffix, and HeLa candidates ranked by mean_cell_count_error_test, ascending (HeLa/06_HeLa_model_ensemble.py:120).
+
+approach="input_ensemble" is the input-ensemble baseline (ISIC_2018/07_ISIC_2018_input_ensemble.py, HeLa/07_HeLa_input_ensemble.py,
+SUIM/08_SUIM_input_ensemble.py, Cityscapes/07_Cityscapes_input_ensemble.py): the model-ensemble loop with ONE model per generation
+(`*_subset_{runid}_topK_1.h5`, then the previous generation's topK_1) voting over n augmented views (create_pseudo_labels_input_ensemble_*),
+n in 3, 5, 7 by default, and the same names, CSVs and ranking."""
 import csv
 import os
 import shutil
@@ -228,7 +233,8 @@ def run(dataset, approach="IM", parallel_candidates=None):
         BI, BO = S["BLOCK_INPUT"].lower() == "true", S["BLOCK_OUTPUT"].lower() == "true"
     filt = S.get("FILTER_INCONSISTENT_CLASS_PRED", "false").lower() == "true"
     aim = approach == "aug_IM_plus"
-    ens = approach == "model_ensemble"
+    inp = approach == "input_ensemble"
+    ens = approach == "model_ensemble" or inp
     rank_idx, rank_desc = (6, False) if (ens and ds["kind"] == "hela") else (ds["rank"], True)
     plus = IM_PLUS[dataset] if approach in ("IM_plus", "aug_IM_plus") else None
     if plus:    # the IM+ scripts parse the blocking flags properly for every dataset (ISIC_2018/11_...IM+.py:38-39)
@@ -243,23 +249,31 @@ def run(dataset, approach="IM", parallel_candidates=None):
     tag = {"HeLa": "HELA", "Cityscapes": "CITYSCAPES"}.get(dataset, dataset)   # name prefix of models / CSVs (HeLa/09_HeLa_IM.py:61)
 
     for runid in _ints("IM_RUNIDS", [1, 2, 3]):
-        for n in _ints("IM_NS", [2, 3, 4]):
+        for n in _ints("IM_NS", [3, 5, 7] if inp else [2, 3, 4]):
             for gen in _ints("IM_GENS", [0, 1, 2, 3, 4]):
                 name_of = lambda g: f"{tag}_{approach}_{runid}_n{n}_gen{g}" + ("" if ens else f"_e{EK}_d{DK}_bi_{BI}_bo_{BO}") + \
                     ("_filtered" if (filt and ds["kind"] == "multi" and not ens) else "")
                 modelname = name_of(gen)
                 out = {k: os.path.join(base, f"{k}_predictions", approach, *(["temp"] if plus else []), modelname)
                        for k in ("val", "test", "train_unlabeled")}
+                n_models = 1 if inp else n       # the input ensemble: one model, n views
                 if gen == 0:
-                    files = [os.path.join(model_dir, f"{tag}_subset{'_aug' if aim else ''}_{runid}_topK_{j}.h5") for j in range(1, n + 1)]
+                    files = [os.path.join(model_dir, f"{tag}_subset{'_aug' if aim else ''}_{runid}_topK_{j}.h5") for j in range(1, n_models + 1)]
                 else:
-                    files = [os.path.join(model_dir, f"{name_of(gen - 1)}_topK_{j}.h5") for j in range(1, n + 1)]
+                    files = [os.path.join(model_dir, f"{name_of(gen - 1)}_topK_{j}.h5") for j in range(1, n_models + 1)]
                 best_models = [F.load_model(f) for f in files]
                 tick = _Timer(f"{modelname}: ")     # IM_TIMING=1 prints the wall time of every stage
 
                 means = []
                 for split, key in (("VAL", "val"), ("TEST", "test"), ("TRAIN_UNLABELED", "train_unlabeled")):
-                    if ens and ds["kind"] == "isic":
+                    if inp and ds["kind"] == "isic":     # USE_N_RND_TRANSFORMATIONS is bool(str): always True (ISIC_2018/07:33)
+                        F.create_pseudo_labels_input_ensemble_ISIC_2018(best_models[0], P(f"{split}_IMAGES_DIR"), out[key], H, W, C, n, True, True)
+                    elif inp and ds["kind"] == "multi":
+                        F.create_pseudo_labels_input_ensemble_multiclass(best_models[0], P(f"{split}_IMAGES_DIR"), out[key], H, W, C, n, True)
+                    elif inp:
+                        F.create_pseudo_labels_input_ensemble_hela(best_models[0], os.path.join(P(f"{split}_DIR"), "brightfield"), out[key],
+                                                                   H, W, C, n)
+                    elif ens and ds["kind"] == "isic":
                         F.create_pseudo_labels_model_ensemble_ISIC_2018(best_models, P(f"{split}_IMAGES_DIR"), out[key], H, W, C, True)
                     elif ens and ds["kind"] == "multi":
                         F.create_pseudo_labels_model_ensemble_multiclass(best_models, P(f"{split}_IMAGES_DIR"), out[key], H, W, C, True)
