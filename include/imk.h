@@ -324,6 +324,28 @@ IMK_API int imk_unet_forward_views_vote(const imk_unet_plan *plan, const float *
                                         int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Noisy-student baseline: the teacher labels an image, then image and label take the same flips / turn
+ * (create_pseudo_labels_noisy_student_*, functions.py:3243-3417; augment_image_and_mask(s), :2725-2826)
+ * ---------------------------------------------------------------------------------------------- */
+/* One call = predict, label and augment for a batch:
+ *   x   [B,H,W,C] u8: what the model is fed;   img [B,H,W,C] u8: what is augmented and written (ISIC: the BGR copy)
+ *   aug device imk_aug_params[B]: image i and its label take aug[i]'s flip_v / flip_h / rot, the image alone the rest
+ *   img_out    [B,H,W,C] u8 = imk_augment(img) (image path)
+ *   labels_out sigmoid head: [B,K,H,W] {0,255}, 255 where p > thr (cmp_ge = 0) or p >= thr (cmp_ge = 1), NaN -> 0;
+ *              softmax head: [B,H,W] class ids by np.argmax's rule (the first maximum; the first NaN wins)
+ *              -- both at the pixel the image's pixel moved to; p are the bits imk_unet_forward writes.
+ * Sigmoid heads with K <= 4 and softmax heads with K <= 64, last decoder widths 8/16/24/32 and H*W a multiple of 16 take one
+ * fused head + label kernel (no fp32 probabilities, no un-moved label) with the image path on a side stream, forked from and
+ * joined to `stream`; the other shapes and imk_unet_plan_debug(materialize) take imk_unet_forward -> label -> imk_augment on
+ * `stream`, with bit-identical outputs.  Asynchronous.  Quarter turns need h == w (set any_quarter_turn if any aug[i].rot is 1
+ * or 3): IMK_EUNSUPPORTED otherwise, before any launch.  The workspace is sized by imk_unet_forward_student_workspace_bytes. */
+IMK_API int64_t imk_unet_forward_student_workspace_bytes(const imk_unet_plan *plan, int batch);
+IMK_API int imk_unet_forward_student(const imk_unet_plan *plan, const float *params, const void *packed, const uint8_t *x,
+                                     const uint8_t *img, int batch, float thr, int cmp_ge, const imk_aug_params *aug,
+                                     int any_quarter_turn, uint8_t *img_out, uint8_t *labels_out, void *workspace,
+                                     int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Evaluation reductions (benchmark_ISIC2018 / benchmark_multiclass)
  * ---------------------------------------------------------------------------------------------- */
 /* Replaces the threshold + per-image numpy metric loop of benchmark_ISIC2018 (functions.py:1120-1140) with

@@ -74,6 +74,9 @@ SIGNATURES = {
     "imk_unet_forward_views_vote_workspace_bytes": (c_int64, [c_void_p, c_int, c_int]),
     "imk_unet_forward_views_vote": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int,
                                             ctypes.c_double, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "imk_unet_forward_student_workspace_bytes": (c_int64, [c_void_p, c_int]),
+    "imk_unet_forward_student": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_int, c_void_p, c_int,
+                                         c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "imk_unet_state_bytes": (c_int64, [c_void_p]),
     "imk_unet_state_init": (c_int, [c_void_p, c_void_p, c_void_p]),
     "imk_unet_fwd_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,

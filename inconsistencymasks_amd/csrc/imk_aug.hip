@@ -9,6 +9,7 @@
 //   * noise: uniform integer in [-m, m) per element from a counter-based hash of (seed, element index) -- the
 //     reference draws from numpy's unseeded global stream, which nothing can reproduce.
 #include "imk_common.h"
+#include "imk_pixmap.h"
 
 namespace {
 
@@ -51,14 +52,7 @@ __global__ __launch_bounds__(256) void augment_kernel(const uint8_t *__restrict_
     else if (k == 7) { wgt[0] = 2; wgt[1] = 7; wgt[2] = 14; wgt[3] = 18; wgt[4] = 14; wgt[5] = 7; wgt[6] = 2; }
     auto src_index = [&](int y_out, int x_out) -> size_t {
         int ys, xs;
-        switch (q.rot) {
-            case 1: ys = H - 1 - x_out; xs = y_out; break;
-            case 2: ys = H - 1 - y_out; xs = W - 1 - x_out; break;
-            case 3: ys = x_out; xs = W - 1 - y_out; break;
-            default: ys = y_out; xs = x_out;
-        }
-        if (q.flip_h) xs = W - 1 - xs;
-        if (q.flip_v) ys = H - 1 - ys;
+        imk_aug_src(q.flip_v, q.flip_h, q.rot, H, W, y_out, x_out, ys, xs);
         return ((size_t)b * H + ys) * W + xs;
     };
     (void)yf; (void)xf;

@@ -165,6 +165,40 @@ struct HeadMfma {
     }
 };
 
+// ---- np.argmax (the model-ensemble, input-ensemble and teacher-label kernels) ----------------------------------------------------------------------------------------------------------------
+// candidates of ascending k: bk < 0 = none yet
+__device__ __forceinline__ void np_argmax_step(float v, int k, float &bv, int &bk) {
+    if (bk < 0) { bv = v; bk = k; return; }
+    if (__builtin_isnan(bv)) return;                   // the first NaN holds
+    if (__builtin_isnan(v) || v > bv) { bv = v; bk = k; }
+}
+// two partial results of disjoint class sets (any order): NaN first, then the larger value, the lower index on ties
+__device__ __forceinline__ void np_argmax_merge(float ov, int ok, float &bv, int &bk) {
+    if (ok < 0) return;
+    if (bk < 0) { bv = ov; bk = ok; return; }
+    const bool on = __builtin_isnan(ov), bn = __builtin_isnan(bv);
+    const bool take = (on || bn) ? (on && (!bn || ok < bk)) : (ov > bv || (ov == bv && ok < bk));
+    if (take) { bv = ov; bk = ok; }
+}
+// np.argmax over the K classes of the lane's pixel in HeadMfma's layout (v[kt][r] = class 16 kt + 4 g + r); the same value on the 4
+// lanes of the pixel
+template <int KT>
+__device__ __forceinline__ int vote_argmax(const f32x4 (&v)[KT], int K) {
+    const int g = (threadIdx.x & 63) >> 4;
+    float bv = 0.f;
+    int bk = -1;
+#pragma unroll
+    for (int kt = 0; kt < KT; ++kt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int k = 16 * kt + 4 * g + r;
+            if (k < K) np_argmax_step(v[kt][r], k, bv, bk);
+        }
+#pragma unroll
+    for (int o = 16; o <= 32; o <<= 1) np_argmax_merge(__shfl_xor(bv, o, 64), __shfl_xor(bk, o, 64), bv, bk);
+    return bk;
+}
+
 // ---- fused head + inconsistency mask (imk_im.hip) -------------------------------------------------------------------------
 #define IMK_HEAD_IM_MAX_MODELS 8
 struct ImkHeadImArgs {
@@ -215,3 +249,20 @@ bool imk_views_vote_head_supported(const ImkViewVoteArgs &a);
 int imk_launch_views_vote_head(const ImkViewVoteArgs &a, hipStream_t stream);
 int imk_vote_views_binary_ld(const float *preds, int n_views, int batch, int h, int w, int k, const int *ops, int ops_ld,
                              double thr, int cmp_ge, uint8_t *masks_out, hipStream_t stream);
+
+// ---- fused head + teacher label moved with the image (imk_student.hip) -----------------------------------------------------
+struct ImkStudentArgs {
+    const f16 *z;                                // last decoder block's conv output [B,H,W,cs]
+    const float *sc, *sh, *wt, *bias;            // its folded BatchNorm; the head's fp32 kernel [cin][K] / bias [K]
+    const imk_aug_params *aug;                   // device [B]: flip_v, flip_h, rot of every image
+    int cin, cs, K, softmax, batch, h, w;
+    float thr;
+    int cmp_ge;                                  // sigmoid: p >= thr or p > thr
+    uint8_t *out;                                // sigmoid: [B,K,H,W] {0,255}; softmax: [B,H,W] class ids -- in the moved frame
+};
+// The shapes of imk_vote_head_supported; the caller takes imk_unet_forward + label + imk_augment otherwise.
+bool imk_student_head_supported(const ImkStudentArgs &a);
+int imk_launch_student_head(const ImkStudentArgs &a, hipStream_t stream);
+// planar label maps [B,P,H,W] -> the same maps moved by aug[b]'s flips / turn (the unfused route of sigmoid heads with P > 1)
+int imk_student_move_planes(const uint8_t *src, int batch, int planes, int h, int w, const imk_aug_params *aug, uint8_t *out,
+                            hipStream_t stream);

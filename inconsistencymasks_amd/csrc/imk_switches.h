@@ -16,6 +16,7 @@ struct ImkSwitches {
     int gemm_ad3_wgs;         // IMK_GEMM_AD3_WGS: largest GEMM-class launch (workgroups) of the deep-look-ahead form, 0 never (default 1024)
     int wgrad_gemm_min;       // IMK_WGRAD_GEMM_MIN: channel threshold of the GEMM-class weight gradient for every size (0, default: the rule)
     bool wgrad_nfo2;          // IMK_WGRAD_NFO2=0: no two-output-tile form of the GEMM-class 3x3 weight gradient
+    bool student_fused;       // IMK_STUDENT_FUSED=0: imk_unet_forward_student takes forward -> label -> imk_augment for every shape
     int side_streams;         // IMK_SIDE_STREAMS: side streams of a training step's weight gradients, 0 ... MAX_SIDE (default 1)
 };
 

@@ -531,6 +531,78 @@ extern "C" int imk_unet_forward_views_vote(const imk_unet_plan *plan, const floa
     return IMK_OK;
 }
 
+// Noisy student: the teacher's forward, the label, and the SAME flips / quarter turn on image and label.  Fused: the last decoder
+// activation goes to a head slab and one kernel (imk_student.hip) applies the output layer, thresholds or arg-maxes, and stores
+// the label in the moved frame, while imk_augment's image path runs on a side stream forked from and joined to `stream`.
+// Unfused (shapes the kernel does not cover, imk_unet_plan_debug(materialize), IMK_STUDENT_FUSED=0): imk_unet_forward -> the single-member vote kernels
+// as the label rule -> imk_augment with the label as its mask (planar maps of a several-map sigmoid head: image alone + the plane
+// mover), all on `stream`.  Workspace: [head slab | un-moved label | activations].
+static size_t student_label_bytes(const imk_unet_plan *plan, int batch) {
+    const imk_unet_cfg &cf = plan->cfg;
+    return up((size_t)batch * cf.h * cf.w * (cf.act_out == 0 ? cf.n_out : 1));
+}
+
+extern "C" int64_t imk_unet_forward_student_workspace_bytes(const imk_unet_plan *plan, int batch) {
+    if (!plan || plan->net != 0 || batch <= 0) return IMK_EINVAL;
+    return (int64_t)(head_slab_bytes(plan, batch, true) + student_label_bytes(plan, batch) + make_ws(plan, batch, 0).total);
+}
+
+extern "C" int imk_unet_forward_student(const imk_unet_plan *plan, const float *params, const void *packed, const uint8_t *x,
+                                        const uint8_t *img, int batch, float thr, int cmp_ge, const imk_aug_params *aug,
+                                        int any_quarter_turn, uint8_t *img_out, uint8_t *labels_out, void *workspace,
+                                        int64_t workspace_bytes, void *stream_) {
+    IMK_CHECK_ARG(plan && plan->net == 0 && params && packed && x && img && aug && img_out && labels_out && workspace && batch > 0);
+    IMK_CHECK_ARG(img != img_out && batch <= 65535);
+    const imk_unet_cfg &cf = plan->cfg;
+    if (any_quarter_turn && cf.h != cf.w) return IMK_EUNSUPPORTED;   // the outputs would change shape: refused before any launch
+    const Ws ws = make_ws(plan, batch, 0);
+    const size_t slab = head_slab_bytes(plan, batch, true), lab = student_label_bytes(plan, batch);
+    if ((int64_t)(slab + lab + ws.total) > workspace_bytes) return IMK_EWORKSPACE;
+    const Topo topo = make_topo(plan);
+    const ImkLayer &o = plan->layers[topo.out];
+    hipStream_t stream = (hipStream_t)stream_;
+    uint8_t *base = (uint8_t *)workspace;
+    const bool sigmoid = cf.act_out == 0;
+    ImkStudentArgs sa{};
+    sa.aug = aug; sa.cin = cf.ch[0]; sa.cs = imk_pad8(cf.ch[0]); sa.K = cf.n_out; sa.softmax = cf.act_out; sa.batch = batch;
+    sa.h = cf.h; sa.w = cf.w; sa.thr = thr; sa.cmp_ge = cmp_ge; sa.out = labels_out;
+    Ctx c{plan, ws, base + slab + lab, params, (const uint8_t *)packed, batch, false, stream};
+    c.x_in[0] = x;
+    if (!plan->dbg_materialize && imk_switches().student_fused && imk_student_head_supported(sa)) {
+        // The augmented image needs only img and the draws: on a side stream beside the forward (blur is the expensive part).  Not for
+        // the narrowest nets (last decoder width 8, ISIC's alpha 0.5): their forward of 32 images takes 0.23 ms, the schedules pair
+        // that width with no blur, and the fork + join then cost more than the image path hides (noisy student).
+        const bool side = sa.cs > 8 && !plan->dbg_single_stream && ensure_side_streams(plan, 1);
+        hipStream_t s_img = side ? plan->side[0] : stream;
+        if (side) {
+            IMK_HIP(hipEventRecord(plan->ev_fork[0], stream));
+            IMK_HIP(hipStreamWaitEvent(s_img, plan->ev_fork[0], 0));
+        }
+        int rc = imk_augment(img, nullptr, batch, cf.h, cf.w, cf.c_in, 0, aug, img_out, nullptr, any_quarter_turn, s_img);
+        if (side) IMK_HIP(hipEventRecord(plan->ev_join[0], s_img));      // recorded even after an error: `stream` is always joined
+        c.ovr_conv = topo.d_c1[3];
+        c.ovr_out = reinterpret_cast<f16 *>(base);
+        sa.z = c.ovr_out; sa.sc = c.bn_scale(topo.d_bnb[3]); sa.sh = c.bn_shift(topo.d_bnb[3]);
+        sa.wt = params + o.off_w; sa.bias = params + o.off_b;
+        if (!rc) rc = run_forward(c, topo, nullptr, nullptr);
+        if (!rc) rc = imk_launch_student_head(sa, stream);
+        if (side) IMK_HIP(hipStreamWaitEvent(stream, plan->ev_join[0], 0));
+        return rc;
+    }
+    float *probs = (float *)base;
+    uint8_t *label = base + slab;
+    int rc = run_forward(c, topo, probs, nullptr);
+    if (rc) return rc;
+    if (sigmoid) rc = imk_vote_views_binary_ld(probs, 1, batch, cf.h, cf.w, cf.n_out, nullptr, 0, thr, cmp_ge, label, stream);
+    else rc = imk_vote_multiclass(probs, 1, batch, cf.h, cf.w, cf.n_out, IMK_VOTE_HARD, label, stream_);
+    if (rc) return rc;
+    if (!sigmoid || cf.n_out == 1)      // one label plane: [B,H,W] is imk_augment's [B,H,W,1] mask
+        return imk_augment(img, label, batch, cf.h, cf.w, cf.c_in, 1, aug, img_out, labels_out, any_quarter_turn, stream_);
+    rc = imk_augment(img, nullptr, batch, cf.h, cf.w, cf.c_in, 0, aug, img_out, nullptr, any_quarter_turn, stream_);
+    if (rc) return rc;
+    return imk_student_move_planes(label, batch, cf.n_out, cf.h, cf.w, aug, labels_out, stream);
+}
+
 // =====================================================================================================
 // training
 // =====================================================================================================

@@ -16,22 +16,6 @@
 
 namespace {
 
-// ---- np.argmax ----------------------------------------------------------------------------------------------------------------
-// candidates of ascending k: bk < 0 = none yet
-__device__ __forceinline__ void np_argmax_step(float v, int k, float &bv, int &bk) {
-    if (bk < 0) { bv = v; bk = k; return; }
-    if (__builtin_isnan(bv)) return;                   // the first NaN holds
-    if (__builtin_isnan(v) || v > bv) { bv = v; bk = k; }
-}
-// two partial results of disjoint class sets (any order): NaN first, then the larger value, the lower index on ties
-__device__ __forceinline__ void np_argmax_merge(float ov, int ok, float &bv, int &bk) {
-    if (ok < 0) return;
-    if (bk < 0) { bv = ov; bk = ok; return; }
-    const bool on = __builtin_isnan(ov), bn = __builtin_isnan(bv);
-    const bool take = (on || bn) ? (on && (!bn || ok < bk)) : (ov > bv || (ov == bv && ok < bk));
-    if (take) { bv = ov; bk = ok; }
-}
-
 // ---- unfused: probability stack -> labels ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void vote_binary_kernel(const float *__restrict__ preds, int n_models, long long n_pix, int hw,
                                                           int kb, double thr, int soft, uint8_t *__restrict__ masks_out) {
@@ -176,23 +160,6 @@ struct VoteUnits { static constexpr int U = KT == 1 ? 8 : (KT == 4 ? 4 : 5); };
 template <int KT, bool SOFT>
 __host__ __device__ constexpr size_t vote_softmax_lds() {
     return (SOFT ? (size_t)4 * VoteUnits<KT>::U * 16 * 16 * KT * sizeof(float) : 0) + (size_t)4 * VoteUnits<KT>::U * 16;
-}
-
-template <int KT>
-__device__ __forceinline__ int vote_argmax(const f32x4 (&v)[KT], int K) {
-    const int g = (threadIdx.x & 63) >> 4;
-    float bv = 0.f;
-    int bk = -1;
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int k = 16 * kt + 4 * g + r;
-            if (k < K) np_argmax_step(v[kt][r], k, bv, bk);
-        }
-#pragma unroll
-    for (int o = 16; o <= 32; o <<= 1) np_argmax_merge(__shfl_xor(bv, o, 64), __shfl_xor(bk, o, 64), bv, bk);
-    return bk;
 }
 
 template <int KT, bool SOFT>

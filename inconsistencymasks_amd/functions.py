@@ -1674,6 +1674,76 @@ def create_pseudo_labels_input_ensemble_multiclass(model, images_path, main_outp
                      lambda name, img, m: [(os.path.join(out["images"], name), img), (os.path.join(out["masks"], name), m)])
 
 
+# ---------------------------------------------------------------------------------------------------
+# Noisy-student baseline (functions.py:3243-3417): the teacher labels the un-augmented image, then image and label take one draw of
+# flips / quarter turn and the image alone brightness, blur and noise.  noisy_student.TeacherLabel runs it per batch
+# (imk_unet_forward_student for a native UNet; predict + label + imk_augment for a duck-typed `.predict` model).
+from . import noisy_student as _ns  # noqa: E402
+
+
+def _run_student_writer(model, images_path, main_output_path, c, binary, thr, cmp_ge, net_sees_file_order, draw_kw, per_image):
+    """Shared body of the noisy-student writers: this rank's shard of the sorted file list in batches, one teacher-label call per
+    batch with each image's draws from (SEED, output directory, file name), the files of every image from
+    per_image(name, augmented image [H,W,C] in the file's channel order, moved label rows) queued on the writer pool."""
+    mine = shard_list(os.listdir(images_path))
+    tl = _ns.TeacherLabel(model, binary)
+    with _pool() as pool:
+        for i, j in infer_batches(len(mine), infer_batch_size(_models_alpha(model))):
+            chunk = mine[i:j]
+            imgs = read_png_stack(pool, [os.path.join(images_path, n) for n in chunk], c)
+            x = torch.from_numpy(imgs).cuda()
+            img = x.flip(-1).contiguous() if c == 3 else x      # the reference augments what cv2.imread returned: BGR
+            params = _ns.pack_params([_ns.draw_for(_view_rngs(main_output_path, n), **draw_kw) for n in chunk])
+            out, lab = tl.run(img if (net_sees_file_order or c != 3) else x, img, params, thr, cmp_ge)
+            out = (out.flip(-1) if c == 3 else out).cpu().numpy()
+            lab = lab.cpu().numpy()
+            jobs = [job for per in pool.map(lambda q: per_image(chunk[q], out[q], lab[q]), range(len(chunk))) for job in per]
+            write_pngs_async(jobs)
+    flush_writes()
+    d = _dist()
+    if d:      # every rank's files are on disk before rank 0 copies the labelled pairs in beside them
+        d.barrier()
+
+
+def create_pseudo_labels_noisy_student_ISIC_2018(model, h, w, c, images_path, main_output_path, rgb=True,
+                                                 brightness_range_alpha=(0.5, 1.5), brightness_range_beta=(-25, 25), max_blur=3,
+                                                 max_noise=25, free_rotation=True):
+    """functions.py:3243-3291: images/ (the augmented image) and masks/ ((p > 0.5) * 255, moved with the image), same file names."""
+    out = _ns.out_dirs(main_output_path, ("images", "masks"))
+    kw = dict(brightness_range_alpha=brightness_range_alpha, brightness_range_beta=brightness_range_beta, max_blur=max_blur,
+              max_noise=max_noise, free_rotation=free_rotation)
+    _run_student_writer(model, images_path, main_output_path, c, True, 0.5, False, not rgb, kw,
+                        lambda name, img, m: [(os.path.join(out["images"], name), img), (os.path.join(out["masks"], name), m[0])])
+
+
+def create_pseudo_labels_noisy_student_hela(model, h, w, c, images_path, main_output_path, brightness_range_alpha=(0.5, 1.5),
+                                            brightness_range_beta=(-25, 25), max_blur=3, max_noise=25, free_rotation=True,
+                                            max_pos_circle_size=8, min_pos_circle_size=3):
+    """functions.py:3295-3364: brightfield/ (augmented), alive/ and dead/ (p >= 0.5 -- moving a map and thresholding it commute),
+    mod_position/ (circles drawn on the MOVED position mask), all named <stem>_aug.png."""
+    out = _ns.out_dirs(main_output_path, ("brightfield", "alive", "dead", "mod_position"))
+    kw = dict(brightness_range_alpha=brightness_range_alpha, brightness_range_beta=brightness_range_beta, max_blur=max_blur,
+              max_noise=max_noise, free_rotation=free_rotation)
+
+    def per_image(name, img, m):
+        name = _ns.aug_name(name)
+        return [(os.path.join(out["brightfield"], name), img), (os.path.join(out["alive"], name), m[0]),
+                (os.path.join(out["dead"], name), m[1]),
+                (os.path.join(out["mod_position"], name), _hela_vote_positions(m[2], max_pos_circle_size, min_pos_circle_size))]
+    _run_student_writer(model, images_path, main_output_path, c, True, 0.5, True, False, kw, per_image)
+
+
+def create_pseudo_labels_noisy_student_multiclass(model, h, w, c, images_path, main_output_path, rgb=True,
+                                                  brightness_range_alpha=(0.5, 1.5), brightness_range_beta=(-25, 25), max_blur=3,
+                                                  max_noise=25, free_rotation=True):
+    """functions.py:3368-3417: images/ (the augmented image) and masks/ (np.argmax class ids as uint8, moved with the image)."""
+    out = _ns.out_dirs(main_output_path, ("images", "masks"))
+    kw = dict(brightness_range_alpha=brightness_range_alpha, brightness_range_beta=brightness_range_beta, max_blur=max_blur,
+              max_noise=max_noise, free_rotation=free_rotation)
+    _run_student_writer(model, images_path, main_output_path, c, False, 0.5, False, not rgb, kw,
+                        lambda name, img, m: [(os.path.join(out["images"], name), img), (os.path.join(out["masks"], name), m)])
+
+
 _HELA_GT_COUNTS = {}      # id(position-mask tensor of a cached decoded set) -> (weak reference to it, [(alive, dead)] ground-truth cell counts)
 
 

@@ -21,7 +21,13 @@ erode / dilate / blocking suffix, and HeLa candidates ranked by mean_cell_count_
 approach="input_ensemble" is the input-ensemble baseline (ISIC_2018/07_ISIC_2018_input_ensemble.py, HeLa/07_HeLa_input_ensemble.py,
 SUIM/08_SUIM_input_ensemble.py, Cityscapes/07_Cityscapes_input_ensemble.py): the model-ensemble loop with ONE model per generation
 (`*_subset_{runid}_topK_1.h5`, then the previous generation's topK_1) voting over n augmented views (create_pseudo_labels_input_ensemble_*),
-n in 3, 5, 7 by default, and the same names, CSVs and ranking."""
+n in 3, 5, 7 by default, and the same names, CSVs and ranking.
+
+approach="noisy_student" is the Noisy-Student baseline (ISIC_2018/08_ISIC_2018_noisy_student.py, HeLa/08_HeLa_noisy_student.py,
+SUIM/09_SUIM_noisy_student.py, Cityscapes/08_Cityscapes_noisy_student.py): ONE teacher per generation (`*_subset_{runid}_topK_1.h5`,
+then the previous generation's topK_1), no n loop and no `_n{n}` in the names, pseudo-labels for train_unlabeled only
+(create_pseudo_labels_noisy_student_*: the label moved with the augmented image), augmentation strength and the U-Net width alpha
+per generation from NOISY_STUDENT, no mean_im_size CSV; HeLa is ranked by index 6 ascending and its CSV header says `mcce_*`."""
 import csv
 import os
 import shutil
@@ -64,6 +70,54 @@ IM_PLUS = {   # per-generation schedules of the IM+ scripts (lines 46-50 / 47-51
                        bra=[(0.95, 1.05), (0.9, 1.1), (0.8, 1.2), (0.7, 1.3), (0.6, 1.4)],
                        brb=[(-3, 3), (-6, 6), (-9, 9), (-12, 12), (-15, 15)]),
 }
+
+
+NOISY_STUDENT = {   # per-generation schedules of the noisy-student scripts (lines 39-43 / 41-45 / 42-46 of each), each from its own script
+    "ISIC_2018": dict(alphas=[0.5, 0.75, 1, 1.25, 1.5], max_blurs=[0, 1, 1, 2, 3], max_noises=[5, 10, 15, 20, 25],
+                      bra=[(0.9, 1.1), (0.8, 1.2), (0.7, 1.3), (0.6, 1.4), (0.5, 1.5)],
+                      brb=[(-5, 5), (-10, 10), (-15, 15), (-20, 20), (-25, 25)]),
+    "SUIM": dict(alphas=[1, 1.25, 1.5, 1.75, 2], max_blurs=[0, 1, 1, 2, 3], max_noises=[5, 10, 15, 20, 25],
+                 bra=[(0.9, 1.1), (0.8, 1.2), (0.7, 1.3), (0.6, 1.4), (0.5, 1.5)],
+                 brb=[(-5, 5), (-10, 10), (-15, 15), (-20, 20), (-25, 25)]),
+    "HeLa": dict(alphas=[1, 1.25, 1.5, 1.75, 2], max_blurs=[0, 1, 1, 2, 3], max_noises=[5, 10, 15, 20, 25],
+                 bra=[(0.9, 1.1), (0.9, 1.1), (0.8, 1.2), (0.8, 1.2), (0.7, 1.3)],
+                 brb=[(-3, 3), (-6, 6), (-9, 9), (-12, 12), (-15, 15)]),
+    "Cityscapes": dict(alphas=[1, 1.25, 1.5, 1.75, 2], max_blurs=[0, 0, 0, 0, 1], max_noises=[3, 6, 9, 12, 15],
+                       bra=[(0.95, 1.05), (0.9, 1.1), (0.8, 1.2), (0.7, 1.3), (0.6, 1.4)],
+                       brb=[(-3, 3), (-6, 6), (-9, 9), (-12, 12), (-15, 15)]),
+}
+# HeLa/08_HeLa_noisy_student.py:143 -- this approach's CSV alone abbreviates the cell-count columns
+NOISY_STUDENT_HELA_HEADER = ["modelname", "mIoU_val", "mIoU_ad_val", "mcce_val", "mIoU_test", "mIoU_ad_test", "mcce_test",
+                             "mIoU_unlabeled", "mIoU_ad_unlabeled", "mcce_unlabeled"]
+
+
+def model_name(tag, approach, runid, n, gen, suffix=""):
+    """`{TAG}_{approach}_{runid}_n{n}_gen{gen}` + suffix; the noisy student has no n (ISIC_2018/08_ISIC_2018_noisy_student.py:56)"""
+    if approach == "noisy_student":
+        return f"{tag}_{approach}_{runid}_gen{gen}"
+    return f"{tag}_{approach}_{runid}_n{n}_gen{gen}{suffix}"
+
+
+def ranking(dataset, approach):
+    """(index of the ranking metric in a candidate's row, descending?) -- the baselines rank HeLa by mean_cell_count_error_test,
+    ascending (HeLa/06_HeLa_model_ensemble.py:120, HeLa/08_HeLa_noisy_student.py:130)"""
+    if approach in ("model_ensemble", "input_ensemble", "noisy_student") and DATASETS[dataset]["kind"] == "hela":
+        return 6, False
+    return DATASETS[dataset]["rank"], True
+
+
+def csv_header(dataset, approach):
+    if approach == "noisy_student" and DATASETS[dataset]["kind"] == "hela":
+        return NOISY_STUDENT_HELA_HEADER
+    return DATASETS[dataset]["header"]
+
+
+def n_values(approach):
+    """the n loop of a generation: views (input ensemble), models (the others); the noisy student has none (one pass, n = 1 teacher)"""
+    inp = approach == "input_ensemble"
+    if approach == "noisy_student":
+        return [1]
+    return _ints("IM_NS", [3, 5, 7] if inp else [2, 3, 4])
 
 
 def default_color_mapping(n_classes):
@@ -234,9 +288,13 @@ def run(dataset, approach="IM", parallel_candidates=None):
     filt = S.get("FILTER_INCONSISTENT_CLASS_PRED", "false").lower() == "true"
     aim = approach == "aug_IM_plus"
     inp = approach == "input_ensemble"
-    ens = approach == "model_ensemble" or inp
-    rank_idx, rank_desc = (6, False) if (ens and ds["kind"] == "hela") else (ds["rank"], True)
+    stu = approach == "noisy_student"
+    ens = approach == "model_ensemble" or inp or stu      # the baselines: no im/ directory, no blocking suffix, no mean_im_size CSV
+    rank_idx, rank_desc = ranking(dataset, approach)
     plus = IM_PLUS[dataset] if approach in ("IM_plus", "aug_IM_plus") else None
+    sched = NOISY_STUDENT[dataset] if stu else None
+    if stu:      # parsed properly in all four scripts (ISIC_2018/08_ISIC_2018_noisy_student.py:44)
+        free_rot = S.get("FREE_ROTATION", "false").lower() == "true"
     if plus:    # the IM+ scripts parse the blocking flags properly for every dataset (ISIC_2018/11_...IM+.py:38-39)
         BI, BO = S["BLOCK_INPUT"].lower() == "true", S["BLOCK_OUTPUT"].lower() == "true"
         filt = filt if (aim and ds["kind"] == "multi") else False      # Cityscapes/13_Cityscapes_aug_IM+.py:42, 68-71
@@ -249,14 +307,14 @@ def run(dataset, approach="IM", parallel_candidates=None):
     tag = {"HeLa": "HELA", "Cityscapes": "CITYSCAPES"}.get(dataset, dataset)   # name prefix of models / CSVs (HeLa/09_HeLa_IM.py:61)
 
     for runid in _ints("IM_RUNIDS", [1, 2, 3]):
-        for n in _ints("IM_NS", [3, 5, 7] if inp else [2, 3, 4]):
+        for n in n_values(approach):
             for gen in _ints("IM_GENS", [0, 1, 2, 3, 4]):
-                name_of = lambda g: f"{tag}_{approach}_{runid}_n{n}_gen{g}" + ("" if ens else f"_e{EK}_d{DK}_bi_{BI}_bo_{BO}") + \
-                    ("_filtered" if (filt and ds["kind"] == "multi" and not ens) else "")
+                name_of = lambda g: model_name(tag, approach, runid, n, g, ("" if ens else f"_e{EK}_d{DK}_bi_{BI}_bo_{BO}") +
+                                               ("_filtered" if (filt and ds["kind"] == "multi" and not ens) else ""))
                 modelname = name_of(gen)
                 out = {k: os.path.join(base, f"{k}_predictions", approach, *(["temp"] if plus else []), modelname)
                        for k in ("val", "test", "train_unlabeled")}
-                n_models = 1 if inp else n       # the input ensemble: one model, n views
+                n_models = 1 if (inp or stu) else n       # the input ensemble: one model, n views; the noisy student: one teacher
                 if gen == 0:
                     files = [os.path.join(model_dir, f"{tag}_subset{'_aug' if aim else ''}_{runid}_topK_{j}.h5") for j in range(1, n_models + 1)]
                 else:
@@ -265,7 +323,21 @@ def run(dataset, approach="IM", parallel_candidates=None):
                 tick = _Timer(f"{modelname}: ")     # IM_TIMING=1 prints the wall time of every stage
 
                 means = []
-                for split, key in (("VAL", "val"), ("TEST", "test"), ("TRAIN_UNLABELED", "train_unlabeled")):
+                if stu:      # train_unlabeled only; val / test get no pseudo-labels
+                    kw = dict(brightness_range_alpha=sched["bra"][gen], brightness_range_beta=sched["brb"][gen],
+                              max_blur=sched["max_blurs"][gen], max_noise=sched["max_noises"][gen], free_rotation=free_rot)
+                    if ds["kind"] == "isic":
+                        F.create_pseudo_labels_noisy_student_ISIC_2018(best_models[0], H, W, C, P("TRAIN_UNLABELED_IMAGES_DIR"),
+                                                                       out["train_unlabeled"], True, **kw)
+                    elif ds["kind"] == "multi":
+                        F.create_pseudo_labels_noisy_student_multiclass(best_models[0], H, W, C, P("TRAIN_UNLABELED_IMAGES_DIR"),
+                                                                        out["train_unlabeled"], True, **kw)
+                    else:
+                        F.create_pseudo_labels_noisy_student_hela(best_models[0], H, W, C,
+                                                                  os.path.join(P("TRAIN_UNLABELED_DIR"), "brightfield"),
+                                                                  out["train_unlabeled"], **kw)
+                    alpha = sched["alphas"][gen]
+                for split, key in (() if stu else (("VAL", "val"), ("TEST", "test"), ("TRAIN_UNLABELED", "train_unlabeled"))):
                     if inp and ds["kind"] == "isic":     # USE_N_RND_TRANSFORMATIONS is bool(str): always True (ISIC_2018/07:33)
                         F.create_pseudo_labels_input_ensemble_ISIC_2018(best_models[0], P(f"{split}_IMAGES_DIR"), out[key], H, W, C, n, True, True)
                     elif inp and ds["kind"] == "multi":
@@ -289,7 +361,8 @@ def run(dataset, approach="IM", parallel_candidates=None):
                     else:
                         means.append(F.create_pseudo_labels_im_hela(best_models, H, W, C, os.path.join(P(f"{split}_DIR"), "brightfield"),
                                                                     out[key], EK, DK, BI, BO))
-                tick("pseudo-labels (val, test, unlabeled): ensemble inference + " + ("vote" if ens else "IM") + " + PNG I/O")
+                tick("pseudo-labels (unlabeled): teacher inference + label + augmentation + PNG I/O" if stu else
+                     "pseudo-labels (val, test, unlabeled): ensemble inference + " + ("vote" if ens else "IM") + " + PNG I/O")
                 unl = out["train_unlabeled"]
                 if plus:     # augmented copies only (copy_org False) form the training set
                     src, unl = unl, os.path.join(base, "train_unlabeled_predictions", approach, modelname)
@@ -351,7 +424,7 @@ def run(dataset, approach="IM", parallel_candidates=None):
                     os.makedirs(csv_dir, exist_ok=True)
                     with open(os.path.join(csv_dir, f"results_{modelname}.csv"), "w", encoding="utf-8", newline="") as f:
                         wr = csv.writer(f, delimiter=";")
-                        wr.writerow(ds["header"])
+                        wr.writerow(csv_header(dataset, approach))
                         wr.writerows(rows)
                     if world > 1:       # the CSV stays byte-compatible with the reference's; what a data-parallel run did differently
                         import json     # goes into a sidecar file
