@@ -403,6 +403,59 @@ IMK_API int imk_evalnet_fwd_bwd(const imk_unet_plan *plan, float *params, void *
 IMK_API int imk_evalnet_tensor_info(const imk_unet_plan *plan, int batch, int mode, int layer_idx, int which,
                             int64_t *byte_offset, int *h, int *w, int *c, int *c_stride);
 
+/* ------------------------------------------------------------------------------------------------
+ * EvalNet-ensemble selection baseline (create_training_data_for_segnet_with_ensemble_binary,
+ * ..._with_miou_ensemble_hela, ..._with_miou_ensemble_multiclass: functions.py:5070-5155, 5323-5577)
+ * ----------------------------------------------------------------------------------------------
+ * For every unlabeled image the reference stacks M candidate masks, scores the (image, mask) pairs with the N EvalNets of the
+ * ensemble, averages over the EvalNets, takes the arg-max candidate and keeps the pair if its score reaches a threshold.  */
+#define IMK_SELECT_MAX_CAND 16    /* candidates per image */
+#define IMK_SELECT_MAX_MODELS 8   /* EvalNets per ensemble */
+enum { IMK_SELECT_IOU = 0, IMK_SELECT_MIOU = 1 };
+
+/* The selection rule and the gather of the chosen candidate, one kernel.
+ *   scores     [N,B,M,n_heads*n_out] f32, unit order of imk_evalnet_forward (iou units first, then detection units)
+ *   counts     device int32 [B] or NULL (= every image has M candidates); candidates m >= counts[b] do not exist for image b and
+ *              influence nothing.  1 <= counts[b] <= M, else IMK_EINVAL (the array is read back before the launch: the call
+ *              waits for `stream` when counts is given)
+ *   cand       [B,M,cand_bytes] u8: what is written out for a chosen candidate; cand_bytes a multiple of 16, cand / out 16-byte aligned
+ *   best_idx [B] int32, best_score [B] f32, keep [B] u8 (0/1), out [B,cand_bytes] u8 = the best candidate's bytes, kept or not
+ * Mean over the models (every mode): ((p_0 + p_1) + p_2) + ... in fp32, then one correctly rounded fp32 divide by N -- np.mean(axis=0)
+ * of the float32 stack, as imk_vote_multiclass.
+ *   IMK_SELECT_IOU  (n_heads = 1, n_out = 1): score = that mean.
+ *   IMK_SELECT_MIOU (n_heads = 2): class k counts if its mean detection >= 0.5f (NaN does not); score = the fp32 sum of the counting
+ *                   classes' mean ious in class order (the first addend as it is), divided by their number (correctly rounded);
+ *                   0 if no class counts.
+ * best_idx = np.argmax of the scores (the first maximum; the first NaN wins); keep = best >= (float)thr (NaN keeps nothing): numpy
+ * compares the float32 score with the Python threshold in float32.
+ * N > IMK_SELECT_MAX_MODELS or M > IMK_SELECT_MAX_CAND (or n_out > 64): IMK_EUNSUPPORTED, before any launch.               */
+IMK_API int imk_evalnet_select(const float *scores, int n_models, int batch, int n_cand, int n_heads, int n_out,
+                               const int32_t *counts, const uint8_t *cand, int64_t cand_bytes, double thr, int mode,
+                               int32_t *best_idx, float *best_score, uint8_t *keep, uint8_t *out, void *stream);
+
+/* N EvalNets of one plan score B images with M candidates each: xa [B,H,W,ca], xb [B,M,H,W,cb] (b_onehot: class ids [B,M,H,W])
+ * -> scores [N,B,M,n_heads*n_out].  Per model the image tower runs once at batch B, the mask tower and the trunk at batch B*M, and
+ * row r of the concatenation reads image r / M of the image tower.  Bit-identical to imk_evalnet_forward on the image repeated M
+ * times.  `params`/`packed` are arrays (host) of n_models device pointers; the models run one after another on `stream`.
+ * Asynchronous; nothing is allocated.  Limits as imk_evalnet_select.  The workspace is one model's activations at batch B*M; under
+ * IMK_SELECT_SHARED=0 it also holds the repeated images, so size it with the function below in the process that makes the call. */
+IMK_API int64_t imk_evalnet_forward_candidates_workspace_bytes(const imk_unet_plan *plan, int batch, int n_cand);
+IMK_API int imk_evalnet_forward_candidates(const imk_unet_plan *plan, int n_models, const float *const *params,
+                                           const void *const *packed, const uint8_t *xa, const uint8_t *xb, int batch, int n_cand,
+                                           float *scores, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* imk_evalnet_forward_candidates + imk_evalnet_select on one stream, the scores staying on the device ([N,B,M,n_heads*n_out], the
+ * caller's buffer) and no host synchronisation between scoring and gather.  Asynchronous with counts = NULL.  With counts given the
+ * call (like imk_evalnet_select) first copies counts to the host and waits for `stream`, so that a count outside 1..M is IMK_EINVAL
+ * rather than a clamp: it then blocks the host once, before its first launch, and cannot be captured into a graph.
+ * Outputs bit-identical to the two calls.  Same workspace.  IMK_SELECT_SHARED=0 (environment) scores through imk_evalnet_forward
+ * per model on a device-side repeat of the images instead: the comparison arm of the tests and the measurement.             */
+IMK_API int imk_evalnet_forward_select(const imk_unet_plan *plan, int n_models, const float *const *params,
+                                       const void *const *packed, const uint8_t *xa, const uint8_t *xb, int batch, int n_cand,
+                                       const int32_t *counts, const uint8_t *cand, int64_t cand_bytes, double thr, int mode,
+                                       float *scores, int32_t *best_idx, float *best_score, uint8_t *keep, uint8_t *out,
+                                       void *workspace, int64_t workspace_bytes, void *stream);
+
 /* Momentum of the BatchNorm moving statistics in the training steps of ONE plan (U-Net or EvalNet).  Default 0.99 = Keras'
  * BatchNormalization default, which the reference never overrides (unet.py:7).  Data-parallel runs with per-GPU batch 32 make
  * N times fewer optimizer steps per epoch: 0.99^N keeps the moving average's memory the same in SAMPLES (functions.py of this

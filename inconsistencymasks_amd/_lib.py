@@ -90,6 +90,14 @@ SIGNATURES = {
                                         ctypes.POINTER(c_int)]),
     "imk_evalnet_fwd_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p,
                                     c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "imk_evalnet_select": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, ctypes.c_double, c_int,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "imk_evalnet_forward_candidates_workspace_bytes": (c_int64, [c_void_p, c_int, c_int]),
+    "imk_evalnet_forward_candidates": (c_int, [c_void_p, c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_void_p, c_void_p,
+                                               c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "imk_evalnet_forward_select": (c_int, [c_void_p, c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_void_p, c_void_p,
+                                           c_int, c_int, c_void_p, c_void_p, c_int64, ctypes.c_double, c_int, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "imk_gather_pairs": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int64, c_int, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
     "imk_augment": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "imk_eval_binary": (c_int, [c_void_p, c_float, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),

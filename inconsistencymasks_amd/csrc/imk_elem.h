@@ -49,8 +49,10 @@ int imk_launch_adamw(float *p, float *m, float *v, const float *g, long long n, 
 // EvalNet (evalnet.py:24-47): concatenation of the towers' pooled BatchNorm outputs; the tail (BN + pool on load, global
 // average pool, Dense + sigmoid head(s), and in training the losses, the gradient of the pooled map and the per-sample
 // Dense gradients) and the batch reduction of the latter
+// a_div > 1: tower A holds B / a_div images and row b of the concatenation reads image b / a_div of it (one image scored
+// with a_div candidate masks: imk_evalnet_forward_candidates)
 int imk_launch_concat_pool(const f16 *za, const float *sca, const float *sha, int csa, const f16 *zb, const float *scb,
-                           const float *shb, int csb, int B, int Hh, int Wh, f16 *cat, hipStream_t stream);
+                           const float *shb, int csb, int B, int Hh, int Wh, f16 *cat, hipStream_t stream, int a_div = 1);
 int imk_launch_onehot(const uint8_t *cls, long long n_pix, int cs, f16 *out, hipStream_t stream);
 size_t imk_evalnet_head_partial_floats(int B, int n_heads, int K, int C);
 int imk_launch_evalnet_head(const f16 *z, const float *sc, const float *sh, const float *const *w, const float *const *bias,

@@ -545,7 +545,7 @@ __global__ __launch_bounds__(256) void concat_pool_kernel(const f16 *__restrict_
                                                           const float *__restrict__ sha, int csa,
                                                           const f16 *__restrict__ zb, const float *__restrict__ scb,
                                                           const float *__restrict__ shb, int csb, int B, int Hh, int Wh,
-                                                          f16 *__restrict__ cat) {
+                                                          f16 *__restrict__ cat, int a_div) {
     const int nc8 = (csa + csb) / 8;
     const long long n = (long long)B * Hh * Wh * nc8;
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -560,7 +560,8 @@ __global__ __launch_bounds__(256) void concat_pool_kernel(const f16 *__restrict_
     const int cs = second ? csb : csa, c0 = second ? c8 * 8 - csa : c8 * 8;
     const float *sc = (second ? scb : sca) + c0, *sh = (second ? shb : sha) + c0;
     const int W = 2 * Wh;
-    const f16 *p = z + ((size_t)(b * 2 * Hh + 2 * y) * W + 2 * x) * cs + c0;
+    const int bz = second ? b : b / a_div;      // tower A: one image for a_div rows of the concatenation
+    const f16 *p = z + ((size_t)(bz * 2 * Hh + 2 * y) * W + 2 * x) * cs + c0;
     const f16x8 v0 = *reinterpret_cast<const f16x8 *>(p), v1 = *reinterpret_cast<const f16x8 *>(p + cs);
     const f16x8 v2 = *reinterpret_cast<const f16x8 *>(p + (size_t)W * cs), v3 = *reinterpret_cast<const f16x8 *>(p + (size_t)W * cs + cs);
     const f16x8 o = imk_affine_pool8(v0, v1, v2, v3, sc, sh);   // the LM_POOL load of the conv kernels
@@ -923,9 +924,11 @@ int imk_launch_adamw(float *p, float *m, float *v, const float *g, long long n, 
 }
 
 int imk_launch_concat_pool(const f16 *za, const float *sca, const float *sha, int csa, const f16 *zb, const float *scb,
-                           const float *shb, int csb, int B, int Hh, int Wh, f16 *cat, hipStream_t stream) {
+                           const float *shb, int csb, int B, int Hh, int Wh, f16 *cat, hipStream_t stream, int a_div) {
+    IMK_CHECK_ARG(a_div >= 1 && B % a_div == 0);
     const long long n = (long long)B * Hh * Wh * ((csa + csb) / 8);
-    imk_klaunch(concat_pool_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, stream, za, sca, sha, csa, zb, scb, shb, csb, B, Hh, Wh, cat);
+    imk_klaunch(concat_pool_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, stream, za, sca, sha, csa, zb, scb, shb, csb, B, Hh, Wh, cat,
+                a_div);
     IMK_LAUNCH_CHECK();
     return IMK_OK;
 }

@@ -105,21 +105,25 @@ Ws make_ews(const imk_unet_plan *p, int B, int mode) {
     return w;
 }
 
-int run_forward(Ctx &c, const ETopo &t, float *params_rw) {
+// a_div > 1 (inference, imk_evalnet_forward_candidates): c.B = B * a_div rows, x_in[0] holds B images -- tower A runs at batch B in
+// the front of its B * a_div sized buffers, and row r of the concatenation reads its image r / a_div
+int run_forward(Ctx &c, const ETopo &t, float *params_rw, int a_div = 1) {
     int rc;
 #define OK(e) do { rc = (e); if (rc) return rc; } while (0)
     const imk_evalnet_cfg &e = c.p->ecfg;
     if (e.b_onehot)
         OK(imk_launch_onehot(c.x_in[1], (long long)c.B * e.h * e.w, imk_pad8(e.cb), reinterpret_cast<f16 *>(c.base + c.ws.onehot),
                              c.stream));
+    const int B_rows = c.B;
     for (int s = 0; s < 2; ++s) {
+        c.B = s == 0 ? B_rows / a_div : B_rows;
         OK(run_conv_fwd(c, t.in_c[s], params_rw));
         OK(run_conv_pair(c, t.t_c3[s], t.t_c1[s], params_rw));
     }
     const int csF = imk_pad8(e.ch[0]);
     OK(imk_launch_concat_pool(c.act(t.t_c1[0]), c.bn_scale(t.t_bn[0]), c.bn_shift(t.t_bn[0]), csF, c.act(t.t_c1[1]),
                               c.bn_scale(t.t_bn[1]), c.bn_shift(t.t_bn[1]), csF, c.B, e.h / 2, e.w / 2,
-                              reinterpret_cast<f16 *>(c.base + c.ws.cat), c.stream));
+                              reinterpret_cast<f16 *>(c.base + c.ws.cat), c.stream, a_div));
     for (int i = 0; i < 5; ++i) OK(run_conv_pair(c, t.m_c3[i], t.m_c1[i], params_rw));
 #undef OK
     return IMK_OK;
@@ -184,6 +188,92 @@ extern "C" int imk_evalnet_forward(const imk_unet_plan *plan, const float *param
     int rc = run_forward(c, t, nullptr);
     if (rc) return rc;
     return run_head(c, t, out, nullptr, nullptr, nullptr);
+}
+
+// ---- EvalNet-ensemble scoring: N models of one plan, B images with M candidate masks each (include/imk.h) -------------------
+namespace {
+
+// Workspace: one model's inference activations at batch B * M (tower A uses the first B images' worth of its buffers).  Only under
+// IMK_SELECT_SHARED=0 (read once per process) the images repeated M times follow: the comparison route alone pays for them.
+struct CandWs { Ws ws; size_t rep = 0, total = 0; };
+CandWs make_cand_ws(const imk_unet_plan *p, int B, int M) {
+    CandWs w;
+    w.ws = make_ews(p, B * M, 0);
+    w.rep = w.ws.total;
+    w.total = w.rep + (imk_switches().select_shared ? 0 : up((size_t)B * M * p->ecfg.h * p->ecfg.w * p->ecfg.ca));
+    return w;
+}
+
+int cand_limits(const imk_unet_plan *plan, int n_models, int batch, int n_cand) {
+    IMK_CHECK_ARG(plan && plan->net == 1 && n_models > 0 && batch > 0 && n_cand > 0);
+    if (n_models > IMK_SELECT_MAX_MODELS || n_cand > IMK_SELECT_MAX_CAND || batch > 65535) return IMK_EUNSUPPORTED;
+    return IMK_OK;
+}
+
+// shared: tower A once per image (run_forward's a_div); else imk_evalnet_forward's launches on the repeated images
+int forward_candidates(const imk_unet_plan *plan, int n_models, const float *const *params, const void *const *packed,
+                       const uint8_t *xa, const uint8_t *xb, int batch, int n_cand, float *scores, void *workspace,
+                       int64_t workspace_bytes, hipStream_t stream, bool shared) {
+    int rc = cand_limits(plan, n_models, batch, n_cand);
+    if (rc) return rc;
+    IMK_CHECK_ARG(params && packed && xa && xb && scores && workspace);
+    for (int n = 0; n < n_models; ++n) IMK_CHECK_ARG(params[n] && packed[n]);
+    const CandWs cw = make_cand_ws(plan, batch, n_cand);
+    if ((int64_t)cw.total > workspace_bytes) return IMK_EWORKSPACE;
+    const imk_evalnet_cfg &e = plan->ecfg;
+    uint8_t *base = (uint8_t *)workspace;
+    if (!shared) {
+        rc = imk_launch_repeat_rows(xa, batch, n_cand, (long long)e.h * e.w * e.ca, base + cw.rep, stream);
+        if (rc) return rc;
+    }
+    const ETopo t = make_etopo(plan);
+    const int rows = batch * n_cand, units = (e.two_heads ? 2 : 1) * e.n_out;
+    for (int n = 0; n < n_models; ++n) {
+        Ctx c{plan, cw.ws, base, params[n], (const uint8_t *)packed[n], rows, false, stream};
+        c.x_in[0] = shared ? xa : base + cw.rep;
+        c.x_in[1] = xb;
+        rc = run_forward(c, t, nullptr, shared ? n_cand : 1);
+        if (rc) return rc;
+        rc = run_head(c, t, scores + (size_t)n * rows * units, nullptr, nullptr, nullptr);
+        if (rc) return rc;
+    }
+    return IMK_OK;
+}
+
+}  // namespace
+
+extern "C" int64_t imk_evalnet_forward_candidates_workspace_bytes(const imk_unet_plan *plan, int batch, int n_cand) {
+    int rc = cand_limits(plan, 1, batch, n_cand);
+    if (rc) return rc;
+    return (int64_t)make_cand_ws(plan, batch, n_cand).total;
+}
+
+extern "C" int imk_evalnet_forward_candidates(const imk_unet_plan *plan, int n_models, const float *const *params,
+                                              const void *const *packed, const uint8_t *xa, const uint8_t *xb, int batch,
+                                              int n_cand, float *scores, void *workspace, int64_t workspace_bytes, void *stream_) {
+    return forward_candidates(plan, n_models, params, packed, xa, xb, batch, n_cand, scores, workspace, workspace_bytes,
+                              (hipStream_t)stream_, true);
+}
+
+extern "C" int imk_evalnet_forward_select(const imk_unet_plan *plan, int n_models, const float *const *params,
+                                          const void *const *packed, const uint8_t *xa, const uint8_t *xb, int batch, int n_cand,
+                                          const int32_t *counts, const uint8_t *cand, int64_t cand_bytes, double thr, int mode,
+                                          float *scores, int32_t *best_idx, float *best_score, uint8_t *keep, uint8_t *out,
+                                          void *workspace, int64_t workspace_bytes, void *stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    int rc = cand_limits(plan, n_models, batch, n_cand);
+    if (rc) return rc;
+    IMK_CHECK_ARG(scores && best_idx && best_score && keep);
+    const imk_evalnet_cfg &e = plan->ecfg;
+    const int n_heads = e.two_heads ? 2 : 1;
+    rc = imk_select_check(n_models, batch, n_cand, n_heads, e.n_out, counts, cand, cand_bytes, mode, out, stream);
+    if (rc) return rc;
+    rc = forward_candidates(plan, n_models, params, packed, xa, xb, batch, n_cand, scores, workspace, workspace_bytes, stream,
+                            imk_switches().select_shared);
+    if (rc) return rc;
+    const ImkSelectArgs a{scores, counts, cand, n_models, batch, n_cand, n_heads, e.n_out, mode == IMK_SELECT_MIOU, cand_bytes,
+                          (float)thr, best_idx, best_score, keep, out};
+    return imk_launch_evalnet_select(a, stream);
 }
 
 extern "C" int imk_evalnet_tensor_info(const imk_unet_plan *plan, int batch, int mode, int layer_idx, int which,

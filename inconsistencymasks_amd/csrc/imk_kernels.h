@@ -194,6 +194,25 @@ struct ImkWgFinalJobs { ImkWgFinalJob j[IMK_WGF_MAX_JOBS]; int n, total_work1, t
 int imk_wgf_add_job(ImkWgFinalJobs &jobs, float *partial, int n_split, int ksize, int cin, int cout, float *dw, float *db);
 int imk_launch_wgrad_finalize_jobs(const ImkWgFinalJobs &jobs, const float *inv_scale_ptr, float *found_inf, hipStream_t stream);
 
+// EvalNet-ensemble selection (imk_select.hip): the launch behind imk_evalnet_select, without its host-side look at `counts`,
+// and the device-side repeat of every image n_rep times ([B][row_bytes] -> [B][n_rep][row_bytes]) of the repeated-image route
+struct ImkSelectArgs {
+    const float *scores;    // [N,B,M,n_heads*n_out]
+    const int32_t *counts;  // [B] or null
+    const uint8_t *cand;    // [B,M,cand_bytes]
+    int n_models, batch, n_cand, n_heads, n_out, miou;
+    long long cand_bytes;
+    float thr;
+    int32_t *best_idx;
+    float *best_score;
+    uint8_t *keep, *out;
+};
+int imk_launch_evalnet_select(const ImkSelectArgs &a, hipStream_t stream);
+// imk_evalnet_select's argument rules (limits, alignment, a read-back of `counts` when given): IMK_OK or the call's error code
+int imk_select_check(int n_models, int batch, int n_cand, int n_heads, int n_out, const int32_t *counts, const uint8_t *cand,
+                     int64_t cand_bytes, int mode, const uint8_t *out, hipStream_t stream);
+int imk_launch_repeat_rows(const uint8_t *src, int batch, int n_rep, long long row_bytes, uint8_t *dst, hipStream_t stream);
+
 // Side streams (training: weight gradients; ensemble inference: one model per stream): ONE pool per device for the whole
 // process, defined in imk_unet.hip.  Stream i of the calling thread's current device, created on first use; nullptr on failure.
 // The first creation also checks GPU_MAX_HW_QUEUES (imk_runtime_warnings, include/imk.h).

@@ -118,6 +118,126 @@ class EvalNet(UNet):
         return out
 
 
+# ---- EvalNet-ensemble selection (imk_evalnet_select / imk_evalnet_forward_select, include/imk.h) -----------------------------
+SELECT_IOU, SELECT_MIOU = 0, 1
+SELECT_MAX_CAND, SELECT_MAX_MODELS = 16, 8
+
+
+def _select_outputs(b, cand):
+    dev = cand.device
+    return (torch.empty(b, dtype=torch.int32, device=dev), torch.empty(b, dtype=torch.float32, device=dev),
+            torch.empty(b, dtype=torch.uint8, device=dev), torch.empty((b,) + tuple(cand.shape[2:]), dtype=torch.uint8, device=dev))
+
+
+def _cand_bytes(cand, b, m):
+    if cand.dtype != torch.uint8 or not cand.is_cuda or cand.dim() < 3 or tuple(cand.shape[:2]) != (b, m):
+        raise TypeError(f"cand must be a uint8 CUDA tensor [{b},{m},...]")
+    return cand[0, 0].numel()
+
+
+def select_candidates(scores, cand, thr, mode, counts=None):
+    """scores float32 [N,B,M,U] (device; U = 1, or the iou units then the detection units), cand uint8 [B,M,...] (device; a multiple
+    of 16 bytes per candidate), counts int32 [B] (device) or None -> (best_idx [B] i32, best_score [B] f32, keep [B] u8, out [B,...] u8):
+    the arg-max candidate by the ensemble's mean IoU (SELECT_IOU) or mean mIoU over the detected classes (SELECT_MIOU), kept where the
+    score reaches thr -- the rule of the reference's create_training_data_for_segnet_with_*ensemble* writers."""
+    if scores.dtype != torch.float32 or scores.dim() != 4 or not scores.is_cuda:
+        raise TypeError("scores must be a float32 CUDA tensor [N,B,M,U]")
+    scores, cand = scores.contiguous(), cand.contiguous()
+    n, b, m, u = scores.shape
+    nbytes = _cand_bytes(cand, b, m)
+    n_heads = 2 if mode == SELECT_MIOU else 1
+    if counts is not None:
+        counts = counts.to(device=scores.device, dtype=torch.int32).contiguous()
+    best_idx, best_score, keep, out = _select_outputs(b, cand)
+    check(lib.imk_evalnet_select(scores.data_ptr(), n, b, m, n_heads, u // n_heads, counts.data_ptr() if counts is not None else None,
+                                 cand.data_ptr(), nbytes, float(thr), mode, best_idx.data_ptr(), best_score.data_ptr(),
+                                 keep.data_ptr(), out.data_ptr(), _stream()), "imk_evalnet_select")
+    return best_idx, best_score, keep, out
+
+
+class CandidateScorer:
+    """The EvalNets of one ensemble + the workspace of imk_evalnet_forward_select.  EvalNets of one architecture take the fused call
+    (the image tower once per image); other ensembles (different plans, duck-typed models with .predict) are scored model by model
+    on the repeated images and go through imk_evalnet_select."""
+
+    def __init__(self, evalnets):
+        self.models = list(evalnets)
+        native = all(isinstance(m, EvalNet) for m in self.models)
+        self.shared = native and all(bytes(m.plan.cfg) == bytes(self.models[0].plan.cfg) for m in self.models)
+        self.n_heads = self.models[0].n_heads if native else None
+        self._ws = {}
+        if self.shared:
+            for m in self.models:
+                m.ready_for_inference()
+            n = len(self.models)
+            self._params = (ctypes.c_void_p * n)(*[m.params.data_ptr() for m in self.models])
+            self._packed = (ctypes.c_void_p * n)(*[m.packed.data_ptr() for m in self.models])
+
+    def _workspace(self, b, m, dev):
+        if (b, m) not in self._ws:
+            nbytes = lib.imk_evalnet_forward_candidates_workspace_bytes(self.models[0].plan.ptr, b, m)
+            if nbytes < 0:
+                check(int(nbytes), "imk_evalnet_forward_candidates_workspace_bytes")
+            self._ws = {(b, m): torch.empty(nbytes, dtype=torch.uint8, device=dev)}
+        return self._ws[(b, m)]
+
+    def scores(self, xa, xb):
+        """xa u8 [B,H,W,Ca], xb u8 [B,M,H,W,Cb] (b_onehot: class ids [B,M,H,W]) on the device -> scores float32 [N,B,M,U]"""
+        xa, xb = xa.contiguous(), xb.contiguous()
+        b, m = xb.shape[:2]
+        if self.shared:
+            p = self.models[0].plan
+            out = torch.empty((len(self.models), b, m, self.n_heads * p.n_out), dtype=torch.float32, device=xa.device)
+            ws = self._workspace(b, m, xa.device)
+            check(lib.imk_evalnet_forward_candidates(p.ptr, len(self.models), self._params, self._packed, xa.data_ptr(), xb.data_ptr(),
+                                                     b, m, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+                  "imk_evalnet_forward_candidates")
+            return out
+        rep = xa.repeat_interleave(m, 0)
+        flat = xb.reshape((b * m,) + tuple(xb.shape[2:]))
+        outs = []
+        for mod in self.models:
+            if hasattr(mod, "predict_device"):
+                fb = flat if flat.dim() == 4 else flat[..., None]
+                o = mod.predict_device(rep, fb.contiguous())
+            else:
+                o = mod.predict([rep.cpu().numpy(), flat.cpu().numpy()])
+                o = np.concatenate([np.asarray(v, np.float32) for v in o], 1) if isinstance(o, (list, tuple)) else np.asarray(o, np.float32)
+                o = torch.from_numpy(np.ascontiguousarray(o)).to(xa.device)
+            outs.append(o.reshape(b, m, -1))
+        return torch.stack(outs, 0).contiguous()
+
+    def run(self, xa, xb, cand, thr, counts=None, mode=None):
+        """-> (best_idx [B], best_score [B], keep [B], out [B,...] = the best candidate's bytes of `cand` [B,M,...])"""
+        if not self.shared:
+            sc = self.scores(xa, xb)
+            if mode is None:
+                mode = SELECT_IOU if sc.shape[-1] == 1 else SELECT_MIOU
+            return select_candidates(sc, cand, thr, mode, counts)
+        if mode is None:
+            mode = SELECT_MIOU if self.n_heads == 2 else SELECT_IOU
+        xa, xb, cand = xa.contiguous(), xb.contiguous(), cand.contiguous()
+        b, m = xb.shape[:2]
+        p = self.models[0].plan
+        nbytes = _cand_bytes(cand, b, m)
+        if counts is not None:
+            counts = counts.to(device=xa.device, dtype=torch.int32).contiguous()
+        scores = torch.empty((len(self.models), b, m, self.n_heads * p.n_out), dtype=torch.float32, device=xa.device)
+        best_idx, best_score, keep, out = _select_outputs(b, cand)
+        ws = self._workspace(b, m, xa.device)
+        check(lib.imk_evalnet_forward_select(p.ptr, len(self.models), self._params, self._packed, xa.data_ptr(), xb.data_ptr(), b, m,
+                                             counts.data_ptr() if counts is not None else None, cand.data_ptr(), nbytes, float(thr),
+                                             mode, scores.data_ptr(), best_idx.data_ptr(), best_score.data_ptr(), keep.data_ptr(),
+                                             out.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), "imk_evalnet_forward_select")
+        self.last_scores = scores
+        return best_idx, best_score, keep, out
+
+
+def score_candidates(evalnets, xa, xb, cand, thr, counts=None, mode=None):
+    """One call of CandidateScorer(evalnets).run(...)."""
+    return CandidateScorer(evalnets).run(xa, xb, cand, thr, counts, mode)
+
+
 def _check_defaults(actifu, ksi, kernel_ini):
     if actifu != "relu" or ksi != 3 or kernel_ini != "he_normal":
         raise NotImplementedError("only the defaults every reference script uses: relu, 3x3, he_normal")

@@ -5,6 +5,7 @@ PNG I/O and the CSV bookkeeping stay on the host.  Re-exported by functions.py."
 import csv
 import os
 import random
+import shutil
 
 import numpy as np
 import torch
@@ -694,3 +695,292 @@ def create_augment_images_and_masks_with_evalnet_ensemble_multiclass(evalnets, h
     F.flush_writes()
     if F._dist():
         F._dist().barrier()
+
+
+# ---------------------------------------------------------------------------------------------------
+# EvalNet-ensemble selection baseline (functions.py:5070-5155, 5323-5577; */1x_*_evalnet*_ensemble.py): for every unlabeled
+# image the candidate masks of several models (and, where one was selected, the last generation's) are scored by the EvalNet
+# ensemble; the candidate with the best mean score is kept if that score reaches the threshold.  Scoring, arg-max, threshold and
+# the gather of the chosen mask are one call per batch (evalnet.CandidateScorer: imk_evalnet_forward_select).
+# ---------------------------------------------------------------------------------------------------
+SELECT_BATCH = int(os.environ.get("IMK_SELECT_BATCH", 8))      # images per call; every image brings up to 11 candidates
+
+
+def _copy_last_generation(last_gen_main_path, main_output_path, subs):
+    """the last generation's selected set goes in first (functions.py:5099-5102); rank 0 copies, the others wait"""
+    F = _F()
+    if last_gen_main_path != '' and F._rank_world()[0] == 0:
+        for name in os.listdir(os.path.join(last_gen_main_path, subs[0])):
+            for k in subs:
+                shutil.copy(os.path.join(last_gen_main_path, k, name), os.path.join(main_output_path, k, name))
+    if F._dist():
+        F._dist().barrier()
+
+
+def _run_selection(evalnets, images_path, c, flip, threshold, load, emit):
+    """Shared body of the selection writers: this rank's shard of the file list in batches of SELECT_BATCH images;
+    load(pool, chunk) -> (input B of the nets u8 [B,M,...], what is written for a candidate u8 [B,M,...], candidates per image);
+    emit(name, chosen bytes) -> PNG jobs of a kept image."""
+    from .evalnet import SELECT_MAX_CAND, CandidateScorer
+    F = _F()
+    scorer = CandidateScorer(evalnets)
+    mine = F.shard_list(os.listdir(images_path))
+    with F._pool() as pool:
+        for s in range(0, len(mine), SELECT_BATCH):
+            chunk = mine[s:s + SELECT_BATCH]
+            x = torch.from_numpy(F.read_png_stack(pool, [os.path.join(images_path, n) for n in chunk], c)).cuda()
+            if flip:
+                x = x.flip(-1).contiguous()
+            xb, cand, counts = load(pool, chunk)
+            b, m = xb.shape[:2]
+            if m > SELECT_MAX_CAND:
+                raise ValueError(f"{m} candidates per image: imk_evalnet_forward_select takes at most {SELECT_MAX_CAND}")
+            cand = cand.reshape(b, m, -1)
+            nbytes = cand.shape[2]
+            if nbytes % 16:      # the gather moves 16 bytes at a time
+                cand = torch.nn.functional.pad(cand, (0, 16 - nbytes % 16))
+            cnt = None if all(v == m for v in counts) else torch.tensor(counts, dtype=torch.int32, device="cuda")
+            _, _, keep, out = scorer.run(x, xb, cand.contiguous(), threshold, cnt)
+            keep, out = keep.cpu().numpy(), out.cpu().numpy()[:, :nbytes]
+            jobs = []
+            for i, name in enumerate(chunk):
+                if keep[i]:
+                    jobs += emit(name, out[i])
+            F.write_pngs_async(jobs)      # encoded while the next batch is decoded and scored
+    F.flush_writes()
+    if F._dist():
+        F._dist().barrier()
+
+
+def _mask_candidates(mask_paths, masks_path_out, h, w, class_ids):
+    """load() of the binary and multi-class writers: one gray PNG per candidate; the file of the same name in the output's masks/
+    (the last generation's choice, copied in before) is one more candidate where it exists (functions.py:5120-5124)"""
+    F = _F()
+
+    def load(pool, chunk):
+        has_last = [os.path.isfile(os.path.join(masks_path_out, n)) for n in chunk]
+        m = len(mask_paths) + int(any(has_last))
+        paths = []
+        for n, hl in zip(chunk, has_last):
+            paths += [os.path.join(d, n) for d in mask_paths]
+            if m > len(mask_paths):      # without a last-generation mask the slot repeats candidate 0 and is excluded by its count
+                paths.append(os.path.join(masks_path_out if hl else mask_paths[0], n))
+        t = torch.from_numpy(F.read_png_stack(pool, paths, 1)).cuda().reshape(len(chunk), m, h, w, 1)
+        return (t[..., 0].contiguous() if class_ids else t), t, [len(mask_paths) + int(hl) for hl in has_last]
+    return load
+
+
+def _takes_class_ids(evalnets):
+    return all(isinstance(e, EvalNet) and e.plan.b_onehot for e in evalnets)
+
+
+def create_training_data_for_segnet_with_ensemble_binary(evalnets, h, w, c, images_path, mask_paths, main_output_path, threshold,
+                                                         last_gen_main_path='', rgb=True):
+    """functions.py:5070-5152: images/ (the file, copied) and masks/ (the candidate with the best mean predicted IoU) of every
+    unlabeled image whose best mean reaches `threshold`."""
+    iout, mout = os.path.join(main_output_path, "images"), os.path.join(main_output_path, "masks")
+    os.makedirs(iout, exist_ok=True)
+    os.makedirs(mout, exist_ok=True)
+    _copy_last_generation(last_gen_main_path, main_output_path, ("images", "masks"))
+
+    def emit(name, chosen):
+        shutil.copy(os.path.join(images_path, name), os.path.join(iout, name))
+        return [(os.path.join(mout, name), chosen.reshape(h, w))]
+    _run_selection(evalnets, images_path, c, (not rgb) and c == 3, threshold, _mask_candidates(mask_paths, mout, h, w, False), emit)
+
+
+def create_training_data_for_segnet_with_miou_ensemble_multiclass(evalnets, h, w, c, num_classes, images_path, mask_paths,
+                                                                  main_output_path, threshold, last_gen_main_path='', rgb=True):
+    """functions.py:5468-5577: as the binary writer with class-id masks; the score of a candidate is the mean of the ensemble's mean
+    predicted IoUs over the classes whose mean detection score is at least 0.5 (0 if there is none)."""
+    iout, mout = os.path.join(main_output_path, "images"), os.path.join(main_output_path, "masks")
+    os.makedirs(iout, exist_ok=True)
+    os.makedirs(mout, exist_ok=True)
+    _copy_last_generation(last_gen_main_path, main_output_path, ("images", "masks"))
+    class_ids = _takes_class_ids(evalnets)
+
+    def emit(name, chosen):
+        shutil.copy(os.path.join(images_path, name), os.path.join(iout, name))
+        return [(os.path.join(mout, name), chosen.reshape(h, w))]
+    load = _mask_candidates(mask_paths, mout, h, w, class_ids)
+    if not class_ids:      # models that take the one-hot stack (functions.py:5528)
+        ids = load
+
+        def load(pool, chunk):
+            xb, cand, counts = ids(pool, chunk)
+            return (xb == torch.arange(num_classes, device=xb.device, dtype=xb.dtype)).to(torch.uint8), cand, counts
+    _run_selection(evalnets, images_path, c, (not rgb) and c == 3, threshold, load, emit)
+
+
+def create_training_data_for_segnet_with_miou_ensemble_hela(evalnets, h, w, c, bf_images_path_in, mask_paths_in, main_output_path,
+                                                            threshold, last_gen_main_path='', max_pos_circle_size=8,
+                                                            min_pos_circle_size=3):
+    """functions.py:5323-5465: the nets see alive / dead / mod_position as 0 / 1 (mask / 255), the chosen alive and dead planes are
+    written as 0 / 255 and the position mask is redrawn from the chosen position plane: a filled circle per blob, radius
+    min_dist // 4 within [min, max], a lone cell drawn with distance 99."""
+    F = _F()
+    planes = ("alive", "dead", "mod_position")
+    out = {k: os.path.join(main_output_path, k) for k in ("brightfield",) + planes}
+    for d in out.values():
+        os.makedirs(d, exist_ok=True)
+    _copy_last_generation(last_gen_main_path, main_output_path, ("brightfield",) + planes)
+
+    def load(pool, chunk):
+        has_last = [last_gen_main_path != '' and os.path.exists(os.path.join(out["alive"], n)) for n in chunk]
+        m = len(mask_paths_in) + int(any(has_last))
+        paths = []
+        for n, hl in zip(chunk, has_last):
+            roots = list(mask_paths_in)
+            if m > len(mask_paths_in):
+                roots.append(main_output_path if hl else mask_paths_in[0])
+            paths += [os.path.join(r, k, n) for r in roots for k in planes]
+        t = torch.from_numpy(F.read_png_stack(pool, paths, 1)).cuda().reshape(len(chunk), m, 3, h, w)
+        m01 = (t.float() / 255.0).round().clamp(0, 255).to(torch.uint8)      # what predict() receives: mask / 255
+        return m01.permute(0, 1, 3, 4, 2).contiguous(), m01 * 255, [len(mask_paths_in) + int(hl) for hl in has_last]
+
+    def emit(name, chosen):
+        alive, dead, pos = chosen.reshape(3, h, w)
+        shutil.copy(os.path.join(bf_images_path_in, name), os.path.join(out["brightfield"], name))
+        return [(os.path.join(out["alive"], name), alive), (os.path.join(out["dead"], name), dead),
+                (os.path.join(out["mod_position"], name), F._hela_vote_positions(pos, max_pos_circle_size, min_pos_circle_size))]
+    _run_selection(evalnets, bf_images_path_in, c, False, threshold, load, emit)
+
+
+# ---------------------------------------------------------------------------------------------------
+# training data of the EvalNets from single models' predictions on the labelled set (functions.py:3419-3492)
+# ---------------------------------------------------------------------------------------------------
+def _pred_name(imagename, i):
+    """functions.py:3466-3472: predictions of the augmented-subset models (i >= 10) on augmented files fold the copy number in"""
+    if i >= 10 and 'aug' in imagename:
+        return f'{imagename[:-10]}___{i}_{imagename[-6:-4]}.png'
+    return f'{imagename[:-4]}___{i}.png'
+
+
+def _append_labels(main_output_path, rows):
+    F = _F()
+    rows = F._gather_lists(rows)[0] if F._dist() else rows
+    if F._rank_world()[0] == 0:
+        with open(os.path.join(main_output_path, 'labels.csv'), 'a', encoding='utf-8', newline='') as f:
+            csv.writer(f, delimiter=';').writerows(rows)
+    if F._dist():
+        F._dist().barrier()
+
+
+def create_training_data_evalnet_ISIC_2018(model, h, w, c, images_path, masks_path, main_output_path, i, rgb=True):
+    """functions.py:3419-3492: masks/<stem>___{i}.png = (p > 0.5) * 255 of every labelled image with its IoU against the ground truth
+    (rounded to 4) appended to labels.csv; for i == 0 also the labelled pairs themselves with IoU 1.0."""
+    from . import evaluate as _ev
+    F = _F()
+    iout, mout = os.path.join(main_output_path, "images"), os.path.join(main_output_path, "masks")
+    os.makedirs(iout, exist_ok=True)
+    os.makedirs(mout, exist_ok=True)
+    names = os.listdir(images_path)
+    mine = F.shard_list(names)
+    rows = []
+    with F._pool() as pool:
+        for s in range(0, len(mine), 64):
+            chunk = mine[s:s + 64]
+            x = torch.from_numpy(F.read_png_stack(pool, [os.path.join(images_path, n) for n in chunk], c)).cuda()
+            g = torch.from_numpy(F.read_png_stack(pool, [os.path.join(masks_path, n) for n in chunk], 1)).cuda()
+            if (not rgb) and c == 3:
+                x = x.flip(-1).contiguous()
+            pred, counts = _ev.eval_binary(model.predict_device(x), g[..., 0].contiguous(), 0.5, False, want_pred=True)
+            pred = pred.cpu().numpy()
+            jobs = []
+            for j, n in enumerate(chunk):
+                jobs.append((os.path.join(mout, _pred_name(n, i)), pred[j]))
+                rows.append((_pred_name(n, i), round(float(_ev.iou_dice_from_counts(counts[j])[0]), 4)))
+            F.write_pngs_async(jobs)
+    F.flush_writes()
+    if i == 0:
+        for n in mine:
+            rows.append((n, 1.0))
+            shutil.copy(os.path.join(images_path, n), os.path.join(iout, n))
+            shutil.copy(os.path.join(masks_path, n), os.path.join(mout, n))
+    _append_labels(main_output_path, rows)
+
+
+def create_training_data_evalnet_miou_hela(model, h, w, c, main_input_path, main_output_path, i, threshold=0.5):
+    """functions.py:4011-4135: alive / dead / mod_position/<stem>___{i}.png = (p > threshold) * 255 of every labelled image, with per
+    plane the IoU against the ground truth (0 where the plane covers less than 1 % of the image, 0.1 % for the positions) and that
+    detection flag appended to labels.csv; for i == 0 also the labelled samples themselves.  The reference's i == 0 loop tests the
+    masks its first loop left behind -- the LAST image's -- for every image; so does this one."""
+    from . import evaluate as _ev
+    F = _F()
+    planes = ("alive", "dead", "mod_position")
+    din = {k: os.path.join(main_input_path, k) for k in ("brightfield",) + planes}
+    dout = {k: os.path.join(main_output_path, k) for k in ("brightfield",) + planes}
+    for d in dout.values():
+        os.makedirs(d, exist_ok=True)
+    names = sorted(os.listdir(din["brightfield"]))      # the writers walk the sorted list; its last image is the one left behind
+    mine = F.shard_list(names)
+    share = (0.01, 0.01, 0.001)
+    rows = []
+    with F._pool() as pool:
+        for s in range(0, len(mine), 64):
+            chunk = mine[s:s + 64]
+            x = torch.from_numpy(F.read_png_stack(pool, [os.path.join(din["brightfield"], n) for n in chunk], c)).cuda()
+            probs = model.predict_device(x)
+            preds, ious, dets = [], [], []
+            for q, k in enumerate(planes):
+                g = torch.from_numpy(F.read_png_stack(pool, [os.path.join(din[k], n) for n in chunk], 1)).cuda()[..., 0].contiguous()
+                pred, counts = _ev.eval_binary(probs[..., q].contiguous(), g, threshold, False, want_pred=True)
+                det = ((g != 0).sum((1, 2)).cpu().numpy() >= h * w * share[q])
+                preds.append(pred.cpu().numpy())
+                dets.append(det)
+                ious.append([float(_ev.iou_dice_from_counts(counts[j])[0]) if det[j] else 0 for j in range(len(chunk))])
+            jobs = []
+            for j, n in enumerate(chunk):
+                pn = _pred_name(n, i)
+                jobs += [(os.path.join(dout[k], pn), preds[q][j]) for q, k in enumerate(planes)]
+                rows.append((pn, ious[0][j], ious[1][j], ious[2][j], int(dets[0][j]), int(dets[1][j]), int(dets[2][j])))
+            F.write_pngs_async(jobs)
+    F.flush_writes()
+    if i == 0 and names:
+        left = [F.read_png(os.path.join(din[k], names[-1]), 1) for k in planes]      # what the first loop's last image left behind
+        det = [int(np.count_nonzero(m) >= h * w * share[q]) for q, m in enumerate(left)]
+        for n in mine:
+            rows.append((n, det[0], det[1], det[2], det[0], det[1], det[2]))
+            for k in ("brightfield",) + planes:
+                shutil.copy(os.path.join(din[k], n), os.path.join(dout[k], n))
+    _append_labels(main_output_path, rows)
+
+
+def create_training_data_evalnet_miou_multiclass(model, h, w, c, num_classes, images_path, masks_path, main_output_path, i, rgb=True):
+    """functions.py:4248-4323: masks/<stem>___{i}.png = the arg-max class ids of every labelled image, with compute_classwise_IoU
+    (called with the ground truth first and the prediction second, as the reference does) and the ground truth's
+    compute_classwise_detection appended to labels.csv; for i == 0 also the labelled pairs, every one with the rows of the LAST
+    image's ground truth against itself (the masks the reference's first loop left behind)."""
+    from . import evaluate as _ev
+    F = _F()
+    iout, mout = os.path.join(main_output_path, "images"), os.path.join(main_output_path, "masks")
+    os.makedirs(iout, exist_ok=True)
+    os.makedirs(mout, exist_ok=True)
+    names = sorted(os.listdir(images_path))      # the writers walk the sorted list; its last image is the one left behind
+    mine = F.shard_list(names)
+    rows = []
+    with F._pool() as pool:
+        for s in range(0, len(mine), 64):
+            chunk = mine[s:s + 64]
+            x = torch.from_numpy(F.read_png_stack(pool, [os.path.join(images_path, n) for n in chunk], c)).cuda()
+            g_np = F.read_png_stack(pool, [os.path.join(masks_path, n) for n in chunk], 1)[..., 0]
+            if (not rgb) and c == 3:
+                x = x.flip(-1).contiguous()
+            pred = _ev.eval_multiclass(model.predict_device(x), torch.from_numpy(g_np).cuda(), want_pred=True)[0].cpu().numpy()
+            stats = list(pool.map(lambda j: (compute_classwise_IoU(g_np[j], pred[j], num_classes),
+                                             compute_classwise_detection(g_np[j], num_classes)), range(len(chunk))))
+            jobs = []
+            for j, n in enumerate(chunk):
+                jobs.append((os.path.join(mout, _pred_name(n, i)), pred[j]))
+                rows.append((_pred_name(n, i), *stats[j][0], *stats[j][1]))
+            F.write_pngs_async(jobs)
+    F.flush_writes()
+    if i == 0 and names:
+        left = F.read_png(os.path.join(masks_path, names[-1]), 1)
+        left = left[..., 0] if left.ndim == 3 else left
+        gt_row = (*compute_classwise_IoU(left, left, num_classes), *compute_classwise_detection(left, num_classes))
+        for n in mine:
+            rows.append((n, *gt_row))
+            shutil.copy(os.path.join(images_path, n), os.path.join(iout, n))
+            shutil.copy(os.path.join(masks_path, n), os.path.join(mout, n))
+    _append_labels(main_output_path, rows)

@@ -1866,7 +1866,11 @@ from .evalnet_functions import (compute_classwise_detection, compute_classwise_d
                                 create_augment_images_and_masks_with_evalnet_ensemble_hela,
                                 create_augment_images_and_masks_with_evalnet_ensemble_multiclass,
                                 create_augment_images_and_masks_with_gt,
-                                create_training_data_evalnet_im_binary, create_training_data_evalnet_miou_im_hela,
-                                create_training_data_evalnet_miou_im_multiclass, load_evalnet, num_augs_from_miou,
+                                create_training_data_evalnet_im_binary, create_training_data_evalnet_ISIC_2018,
+                                create_training_data_evalnet_miou_hela, create_training_data_evalnet_miou_im_hela,
+                                create_training_data_evalnet_miou_im_multiclass, create_training_data_evalnet_miou_multiclass,
+                                create_training_data_for_segnet_with_ensemble_binary,
+                                create_training_data_for_segnet_with_miou_ensemble_hela,
+                                create_training_data_for_segnet_with_miou_ensemble_multiclass, load_evalnet, num_augs_from_miou,
                                 save_evalnet, train_evalnet_ISIC_2018, train_evalnet_miou_model_hela,
                                 train_evalnet_miou_model_multiclass)
