@@ -66,9 +66,9 @@ IMK_API int imk_im_binary(const float *preds, int n_models, int batch, int h, in
                   uint8_t *img_out, uint8_t *masks_out, uint8_t *im_out,
                   int64_t *im_size, int64_t *pred_size, void *stream);
 
-/* Multi-class IM.  Replaces get_im_prediction_multiclass (functions.py:3206-3238: argmax, first
- * maximum wins), pred_masks_to_im_multiclass (functions.py:3123-3137) and the blocking of
- * functions.py:3055-3062.
+/* Multi-class IM.  Replaces get_im_prediction_multiclass (functions.py:3206-3238), pred_masks_to_im_multiclass
+ * (functions.py:3123-3137) and the blocking of functions.py:3055-3062.  The arg-max is np.argmax's: the first maximum
+ * wins, and a NaN counts as the maximum (the first NaN wins).
  *   probs      [N,B,H,W,K] float32, K <= 64
  *   final_out  [B,H,W] uint8 class ids (0 where the models disagree; zeroed on IM pixels if block_out --
  *              the same thing, kept for symmetry with the reference's order of operations)
@@ -358,7 +358,8 @@ IMK_API int imk_eval_binary(const float *probs, float thr, int cmp_ge, const uin
 /* Replaces argmax + pixel_accuracy (functions.py:1820-1834) + get_IoU_multi_unique (:1791-1816) of
  * benchmark_multiclass (:1308-1330):  probs [B,H,W,K] f32, gt [B,H,W] u8 class ids -> pred_out [B,H,W] u8 (may be
  * NULL), counts [B,4,256] int64: [0][v] = #(gt==v), [1][v] = #(pred==v), [2][v] = #(gt==v & pred==v),
- * [3][0] = #(pred==gt).  k <= 256. */
+ * [3][0] = #(pred==gt).  k <= 256.  The arg-max is np.argmax's: the first maximum wins, and a NaN counts as the maximum
+ * (the first NaN wins). */
 IMK_API int imk_eval_multiclass(const float *probs, const uint8_t *gt, int batch, int h, int w, int k, uint8_t *pred_out,
                         int64_t *counts, void *stream);
 

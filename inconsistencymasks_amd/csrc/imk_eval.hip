@@ -5,6 +5,7 @@
 // the host forms the ratios with the reference's own float expressions, so results are bit-identical.
 // HBM-bound: probabilities read once, mask written once, counts via LDS histograms + one atomic per bin per block.
 #include "imk_common.h"
+#include "imk_head.h"
 
 namespace {
 
@@ -88,12 +89,9 @@ __global__ __launch_bounds__(256) void eval_multi_kernel(const float *__restrict
         const int p = p0 + threadIdx.x;
         if (p < hw) {
             const float *q = s_p + threadIdx.x * pitch;
-            float best = q[0];
-            int arg = 0;
-            for (int k = 1; k < K; ++k) {        // first maximum wins (np.argmax); inputs are finite
-                const float v = q[k];
-                if (v > best) { best = v; arg = k; }
-            }
+            float best = 0.f;
+            int arg = -1;
+            for (int k = 0; k < K; ++k) np_argmax_step(q[k], k, best, arg);   // np.argmax: the first maximum, the first NaN wins
             const int g = gt[base + p];
             if (pred_out) pred_out[base + p] = (uint8_t)arg;
             atomicAdd(&hist[g], 1u);

@@ -188,7 +188,8 @@ __global__ __launch_bounds__(256) void im_binary_generic(
 // ---- multiclass ----------------------------------------------------------------------------------
 // grid (ceil(HW/256), B), dynamic LDS = 256 * (K|1) floats.  Each model's [256 px][K] slab is read
 // with coalesced 16-byte loads into LDS (odd row stride: conflict-free column walks), then one thread
-// per pixel takes the arg-max (strict >, so the lowest index wins ties like numpy).
+// per pixel takes np.argmax (np_argmax_step, imk_head.h: the first maximum wins, and a NaN counts as the maximum -- the
+// first NaN wins).
 __global__ __launch_bounds__(256) void im_multi_kernel(
     const float *__restrict__ probs, int n_models, int batch, int hw, int k_classes, uint32_t magic_k,
     const uint8_t *__restrict__ img, int c, int block_in, int block_out,
@@ -231,12 +232,9 @@ __global__ __launch_bounds__(256) void im_multi_kernel(
         __syncthreads();
         if (t < n_px) {
             const float *row = s_p + t * ks;
-            int best = 0;
-            float bv = row[0];
-            for (int k = 1; k < k_classes; ++k) {
-                const float v = row[k];
-                if (v > bv) { bv = v; best = k; }
-            }
+            int best = -1;
+            float bv = 0.f;
+            for (int k = 0; k < k_classes; ++k) np_argmax_step(row[k], k, bv, best);
             s_pres[best] = 1;
             if (n == 0) label0 = best; else agree = agree && (best == label0);
         }

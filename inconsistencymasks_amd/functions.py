@@ -345,7 +345,10 @@ def pred_masks_to_im_binary(pred_masks):
 
 
 def pred_masks_to_im_multiclass(pred_masks):
-    """functions.py:3123-3137.  pred_masks: list of N integer label maps [1,H,W] / [H,W]."""
+    """functions.py:3123-3137.  pred_masks: list of N integer label maps [1,H,W] / [H,W].
+    Returns (final u8 [H,W] class ids, im u8 [H,W] {0,255}, im_size).  The maps go to the kernel as one-hot rows of
+    labels.max() + 1 classes, and imk_im_multiclass takes at most 64: a label >= 64 raises ImkError ("unsupported shape").
+    The reference has no such limit."""
     labels = np.stack([np.asarray(m).reshape(np.asarray(m).shape[-2:]) for m in pred_masks], 0)
     k = int(labels.max()) + 1
     onehot = np.eye(k, dtype=np.float32)[labels]                          # argmax(onehot) == label

@@ -79,7 +79,7 @@ def im_binary(preds, thr=0.5, cmp_ge=False):
 
 def argmax_first(probs):
     """argmax over the last axis, lowest index on ties (numpy semantics the reference relies on,
-    functions.py:3225).  NaN is treated as the maximum by numpy; callers must keep inputs finite."""
+    functions.py:3225).  NaN is treated as the maximum by numpy, so the first NaN wins; the kernels follow that."""
     return np.argmax(np.asarray(probs), axis=-1)
 
 

@@ -38,6 +38,11 @@ def test_eval_multiclass(shape, K):
     probs[..., 0][probs[..., 0] > 0.9] = 2.0
     if K > 2:
         probs[0, :, :, 2] = probs[0, :, :, 1]                  # ties: the first maximum wins
+    flat = probs.reshape(-1, K)                                # NaN counts as the maximum, the first NaN wins (np.argmax)
+    flat[1::11, K - 1] = np.nan
+    flat[2::13, K // 2] = np.nan
+    flat[3::17, 0] = np.nan
+    flat[4::19] = np.nan
     gt = rng.integers(0, K + 1, shape).astype(np.uint8)        # includes an id the net never predicts
     gt[-1] = 255 if K < 255 else 0
     pred, counts = E.eval_multiclass(torch.from_numpy(probs).cuda(), torch.from_numpy(gt).cuda())

@@ -181,7 +181,8 @@ def test_randomized_shapes_vs_oracle(im):
     """60 random cases (seeded): models 2-6, batch 1-4, ragged sizes that exercise the vector / generic paths and partial
     workgroups, 1-5 sigmoid maps or 2-40 classes, thresholds incl. exact ties with the data, image channels 1 / 3 / none,
     every blocking combination; probabilities salted with the values SURVEY 8a' lists (0.5, neighbours of 0.5, 0, 1, -0.0,
-    inf, denormals; NaN only for the binary chain, where the comparison defines its vote).  Bit-exact against the oracle."""
+    inf, denormals, NaN: the comparison defines NaN's vote in the binary chain, np.argmax its label in the multiclass one).
+    Bit-exact against the oracle."""
     rng = np.random.default_rng(2024)
     special = np.array([0.5, np.nextafter(np.float32(0.5), np.float32(1)), np.nextafter(np.float32(0.5), np.float32(0)),
                         0.0, 1.0, -0.0, np.inf, -np.inf, 1e-38, 0.25, 0.75], np.float32)
@@ -218,7 +219,7 @@ def test_randomized_shapes_vs_oracle(im):
             p[:, :, : h // 2] = np.round(p[:, :, : h // 2] * 4) / 4          # exact ties between classes
             flat = p.reshape(-1)
             idx = rng.choice(flat.size, size=max(1, flat.size // 10), replace=False)
-            flat[idx] = special[rng.integers(0, len(special), idx.size)]
+            flat[idx] = np.concatenate([special, [np.nan]]).astype(np.float32)[rng.integers(0, len(special) + 1, idx.size)]
             r = im.im_multiclass(torch.from_numpy(p).cuda(), imgd, bi, bo)
             for i in range(b):
                 e = O.im_multiclass(p[:, i])
