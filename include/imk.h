@@ -19,6 +19,17 @@
  *     The debug switches at the end of this file act on ONE plan (imk_unet_plan_debug); the measurement context
  *     (imk_prof_*) is created and owned by the caller and bound to the launching thread.
  *   - images and masks are uint8, NHWC; probabilities float32 NHWC; sizes int64.
+ *
+ * Buffers (all entry points; tests/test_gpu_buffer_contract.py holds every one of them to this with guard bands and poison fills):
+ *   - what workspaces and outputs hold on entry is arbitrary: the library initialises what it needs on `stream` inside the call
+ *     (counters, sums, tile schedules), and no result depends on what a workspace or an output held before -- a workspace may be
+ *     shared between calls on one stream and need never be cleared;
+ *   - nothing outside [ptr, ptr + bytes) of any argument is written, where bytes is the size this header gives for the argument
+ *     (for workspaces, packed weights and optimizer state: what the matching *_bytes query returns);
+ *   - `const` arguments are not modified;
+ *   - every byte of an output is written, except where an output is stated to be unused on a route: such a buffer is not touched
+ *     and may be NULL;
+ *   - a workspace smaller than the call needs is refused with IMK_EWORKSPACE before anything is launched or written.
  */
 #ifndef IMK_H
 #define IMK_H
@@ -161,7 +172,8 @@ IMK_API int imk_unet_layer_info(const imk_unet_plan *plan, int idx, imk_layer_in
 
 /* fp16 copies of the conv kernels in MFMA-fragment order (forward and transposed/flipped for dgrad),
  * folded BN scale/shift.  Re-run after every change of `params`.  train = 0 folds the moving statistics
- * into scale/shift (inference); in training the batch statistics are produced by the step itself. */
+ * into scale/shift (inference); in training the batch statistics are produced by the step itself.
+ * Every byte of `packed` is written (the gaps of its layout are zeroed): it is a function of `params` alone. */
 IMK_API int64_t imk_unet_packed_bytes(const imk_unet_plan *plan);
 IMK_API int imk_unet_pack_weights(const imk_unet_plan *plan, const float *params, void *packed, void *stream);
 
@@ -186,7 +198,7 @@ IMK_API int imk_unet_tensor_info(const imk_unet_plan *plan, int batch, int mode,
  * to imk_unet_forward + imk_im_binary / imk_im_multiclass.  One call = functions.py:2844-2887 minus file I/O, for a batch.
  * `params`/`packed` are arrays (host) of n_models device pointers.
  * binary heads (act_out = 0): outputs as imk_im_binary;  softmax heads: as imk_im_multiclass
- * (masks_out = final_out [B,H,W], pred_size unused, presence optional).
+ * (masks_out = final_out [B,H,W]; pred_size unused: not written on either route, may be NULL; presence optional).
  * workspace: imk_unet_forward_im_workspace_bytes(plan, n_models, B, k), 1 <= k <= min(n_models, 3): with k > 1 the models
  * run on k streams side by side (forked from and joined to `stream` with events; the call stays asynchronous), with
  * k = 1 back to back.  Shapes the fused kernel does not cover (sigmoid heads with more than 4 maps, H*W not a multiple
@@ -316,7 +328,9 @@ enum { IMK_VOTE_MAJORITY = 2 };
  * Outputs are bit-identical to imk_unet_forward over the views + imk_vote_views_binary / imk_vote_binary / imk_vote_multiclass /
  * imk_vote_views_majority, which is the route for the shapes the fused kernels do not cover: there the forwards run per view
  * and image chunk so that the fp32 stack of the whole batch is never held.  The workspace is sized by
- * imk_unet_forward_views_vote_workspace_bytes(plan, M, B). */
+ * imk_unet_forward_views_vote_workspace_bytes(plan, M, B).  A smaller one is accepted down to
+ * align256(M*H*W*n_out*4) + imk_unet_workspace_bytes(plan, 1, 0): the call then takes the unfused route in image chunks that fit
+ * (one image per chunk at that size), with the same outputs; below that, IMK_EWORKSPACE. */
 IMK_API int64_t imk_unet_forward_views_vote_workspace_bytes(const imk_unet_plan *plan, int n_views, int batch);
 IMK_API int imk_unet_forward_views_vote(const imk_unet_plan *plan, const float *params, const void *packed,
                                         const uint8_t *views, int n_views, int batch, const int *ops, int any_quarter_turn,

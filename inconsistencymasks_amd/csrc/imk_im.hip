@@ -508,7 +508,8 @@ int imk_launch_head_im(const ImkHeadImArgs &a, hipStream_t stream) {
     if (!imk_head_im_supported(a)) return IMK_EUNSUPPORTED;
     const int nf = a.softmax ? 1 : a.K;
     IMK_HIP(hipMemsetAsync(a.im_size, 0, sizeof(int64_t) * a.batch * nf, stream));
-    if (a.pred_size) IMK_HIP(hipMemsetAsync(a.pred_size, 0, sizeof(int64_t) * a.batch * nf, stream));
+    // softmax heads have no pred_size (include/imk.h): the buffer is not touched, as on the unfused route (imk_im_multiclass)
+    if (a.pred_size && !a.softmax) IMK_HIP(hipMemsetAsync(a.pred_size, 0, sizeof(int64_t) * a.batch * nf, stream));
     if (a.softmax && a.presence) IMK_HIP(hipMemsetAsync(a.presence, 0, (size_t)a.n_models * a.batch * a.K, stream));
     const size_t lds = head_im_lds(a);
     const int chunk = a.softmax ? MC_CHUNK : BIN_CHUNK;

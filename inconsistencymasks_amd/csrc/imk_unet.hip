@@ -273,6 +273,10 @@ extern "C" int64_t imk_unet_packed_bytes(const imk_unet_plan *plan) { return pla
 
 
 extern "C" int imk_unet_pack_weights(const imk_unet_plan *plan, const float *params, void *packed, void *stream_) {
+    IMK_CHECK_ARG(plan && params && packed);
+    // The layout has bytes no packing job writes (alignment gaps, the unused tail of a chain slot, the output layer's forward copy:
+    // the head reads `params`).  They are zeroed so that `packed` is a function of `params` alone, whatever the buffer held.
+    IMK_HIP(hipMemsetAsync(packed, 0, (size_t)plan->packed_bytes, (hipStream_t)stream_));
     return pack_weights(plan, params, packed, (hipStream_t)stream_, nullptr, nullptr, true);
 }
 
