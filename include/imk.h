@@ -250,6 +250,26 @@ IMK_API int imk_unet_adamw_step(const imk_unet_plan *plan, float *params, void *
                         const float *grads, const float *stats, float grad_scale,
                         float lr, float wd, float beta1, float beta2, float eps, void *stream);
 
+/* Consistency-loss step (functions.py:367-474 of the reference; the unlabelled half of an epoch of the consistency-loss
+ * baseline): x1, x2 u8 [B,H,W,c_in] are two views of one unlabelled batch (imk_views with two views); both forwards run in training
+ * mode, each BatchNorm normalising with the statistics of its own view's batch, and the moving statistics in `params` move twice,
+ * view 1 first.  L = mean over B*H*W*n_out of (p1 - p2)^2 on the fp32 outputs of the sigmoid / softmax head, the gradient taken
+ * through both forwards (and through the softmax).  grads, stats, state: as imk_unet_fwd_bwd, stats[0] = L; follow with
+ * imk_unet_adamw_step, so that labelled and consistency steps share Adam's slots, the step counter and the dynamic loss scale
+ * (the fp16 gradient tensors carry the state's loss scale; an overflowing step is skipped like a labelled one).
+ * Order on `stream`: forward of view 1, forward of view 2, the consistency head, backward of view 1 into `grads`, backward of
+ * view 2 into a second vector inside the workspace, one fixed-order grads += second.  No float atomics: bit-reproducible.
+ * Sigmoid heads with 1 or 3 maps on a last decoder width of 8 or 16 (padded) channels take one fused head kernel that reads both
+ * last activations once; every other shape, plans with the materialize debug switch and IMK_CONSISTENCY_FUSED=0 take the composed
+ * route (both fp32 probability stacks -> both logit gradients -> the labelled step's head dgrad per view).
+ * workspace: imk_unet_consistency_workspace_bytes(plan, B) = two training workspaces, the second gradient vector and the head's
+ * scratch; view v's training workspace starts at byte v * imk_unet_workspace_bytes(plan, B, 1), so imk_unet_tensor_info(mode 1)
+ * offsets are valid relative to that.                                                                                   */
+IMK_API int64_t imk_unet_consistency_workspace_bytes(const imk_unet_plan *plan, int batch);
+IMK_API int imk_unet_consistency_fwd_bwd(const imk_unet_plan *plan, float *params, void *packed, void *state,
+                                 const uint8_t *x1, const uint8_t *x2, int batch,
+                                 float *grads, float *stats, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Noisy-Student augmentation (IM+ / AIM+ drivers)
  * ---------------------------------------------------------------------------------------------- */

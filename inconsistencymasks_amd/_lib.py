@@ -81,6 +81,9 @@ SIGNATURES = {
     "imk_unet_state_init": (c_int, [c_void_p, c_void_p, c_void_p]),
     "imk_unet_fwd_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                  c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "imk_unet_consistency_workspace_bytes": (c_int64, [c_void_p, c_int]),
+    "imk_unet_consistency_fwd_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                             c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "imk_evalnet_plan_create": (c_int, [ctypes.POINTER(EvalnetCfg), ctypes.POINTER(c_void_p)]),
     "imk_evalnet_workspace_bytes": (c_int64, [c_void_p, c_int, c_int]),
     "imk_evalnet_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64,

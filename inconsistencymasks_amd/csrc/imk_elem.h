@@ -42,6 +42,18 @@ int imk_launch_head_mse_fused(const f16 *z, const float *sc, const float *sh, co
                               int K, long long n_pix, const uint8_t *y, const ImkCtl *ctl, float *stats, f16 *dy,
                               float *loss_partial, float *dystat_partial, float *wg_partial, hipStream_t stream);
 int imk_launch_loss_finalize(const float *loss_partial, long long n_pix, int K, int kind, float *stats, hipStream_t stream);
+// consistency-loss step (imk_consist.hip): L = mean (pA - pB)^2 over two views' head outputs.  Fused (sigmoid heads, 1 or 3 maps on
+// 8 / 16 padded channels): head of both views + loss + both BatchNorm-output gradients with their statistics rows + one set of
+// weight-gradient rows for the output layer, imk_loss_blocks(n_pix) rows each.  Composed: both fp32 probability stacks -> both fp16
+// logit gradients [n_pix][pad8(K)] + loss partials.  imk_launch_grad_add: g += g2 in one fixed order (non-finite sums set *found_inf).
+bool imk_consistency_fused_ok(int cs, int K, int softmax, long long n_pix, int rows_cap);
+int imk_launch_consistency_head(const f16 *zA, const f16 *zB, const float *scA, const float *shA, const float *scB,
+                                const float *shB, const float *w, const float *bias, int cin, int cs, int K, long long n_pix,
+                                const ImkCtl *ctl, float *stats, f16 *dyA, f16 *dyB, float *loss_partial, float *dystatA,
+                                float *dystatB, float *wg_partial, hipStream_t stream);
+int imk_launch_consistency_dlogit(const float *pA, const float *pB, int K, int softmax, long long n_pix, const ImkCtl *ctl,
+                                  float *stats, f16 *dlogitA, f16 *dlogitB, float *loss_partial, hipStream_t stream);
+int imk_launch_grad_add(float *g, const float *g2, long long n, float *found_inf, hipStream_t stream);
 int imk_launch_ctl_init(ImkCtl *ctl, hipStream_t stream);
 int imk_launch_adamw(float *p, float *m, float *v, const float *g, long long n, ImkCtl *ctl, const float *stats,
                      float grad_scale, float lr, float wd, float b1, float b2, float eps, hipStream_t stream);

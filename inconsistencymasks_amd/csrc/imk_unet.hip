@@ -623,6 +623,110 @@ extern "C" int imk_unet_state_init(const imk_unet_plan *plan, void *state, void 
     return imk_launch_ctl_init(state_view(plan, state).ctl, stream);
 }
 
+namespace {
+
+// The output layer's weight / bias gradient as partial rows some head kernel has already written (run_backward queues their reduction).
+struct HeadWgJob { float *partial; int rows; };
+
+// The head's dgrad / weight-gradient launches of a step whose logit gradient is a stored tensor (the labelled step where no one-pass
+// head kernel covers the shape; both views of the consistency step's composed route).  *rows: statistics rows of the last BatchNorm's
+// dy; *job: set where the dgrad launch produced the weight-gradient rows itself.
+template <typename LossHook>
+int head_dgrad(Bwd &b, const Topo &t, f16 *dlogit, LossHook &&loss_on_side, int *head_rows, HeadWgJob *job) {
+    Ctx &c = b.c;
+    const imk_unet_cfg &cf = c.p->cfg;
+    const ImkLayer &ol = c.p->layers[t.out];
+    const int obn = t.d_bnb[3];
+    int rc;
+#define OK(e) do { rc = (e); if (rc) return rc; } while (0)
+    // head: its "dA" is dlogit.  Its dgrad (dlogit -> dy of the last BatchNorm, with that BN's gradient statistics) reads
+    // exactly the operands of its weight gradient (dlogit, and z = the last decoder activation, whose BatchNorm output is
+    // the head's input): where the pipelined kernel covers the shape, one launch produces both.
+    ImkConvArgs ha{};
+    ha.x.in = dlogit; ha.x.lmode = LM_RAW; ha.x.cin = ol.cout; ha.x.cs_in = imk_pad8(ol.cout);
+    ha.B = c.B; ha.H = cf.h; ha.W = cf.w; ha.ksize = 1; ha.cout = ol.cin; ha.cs_out = imk_pad8(ol.cin);
+    ha.wpk = c.wbwd(t.out); ha.out = c.dy(obn); ha.epi = EP_PLAIN;
+    ha.dystat_z = c.act(t.d_c1[3]);
+    ha.stats_partial = reinterpret_cast<float *>(c.base + c.ws.L[obn].bwd_partial);
+    const bool head_fused = imk_conv_can_fuse_wgrad(ha);
+    if (!head_fused) OK(b.wgrad(t.out, dlogit));
+    // the loss value only needs head_loss_kernel's partials: its reduction rides on the side stream, behind the head's
+    // weight gradient, instead of sitting at the end of the step
+    OK(loss_on_side());
+    int rows = 0;
+    ha.stats_rows = &rows;
+    if (head_fused) {
+        ha.wg_partial = reinterpret_cast<float *>(c.base + c.ws.L[t.out].wg_partial);
+        ha.wg_sc = c.bn_scale(obn); ha.wg_sh = c.bn_shift(obn);
+    }
+    OK(imk_launch_conv(ha, c.stream));
+    if (rows <= 0 || rows > c.ws.L[obn].n_bwd_rows) return IMK_EWORKSPACE;
+    *head_rows = rows;
+    if (head_fused) {
+        if (rows > imk_conv_fused_wgrad_rows_max()) return IMK_EWORKSPACE;
+        *job = HeadWgJob{ha.wg_partial, rows};
+    }
+#undef OK
+    return IMK_OK;
+}
+
+// Everything of a backward pass below the head: decoders 9..6, bottleneck, encoders 4..1, input block, and the reduction of every
+// weight gradient into b.grads.  On entry the last BatchNorm's dy is stored with `head_rows` rows of its gradient statistics, and
+// `head_job` (optional) holds the output layer's weight-gradient rows.  loss_on_side: called wherever a fork to the side stream exists.
+template <typename LossHook>
+int run_backward(Bwd &b, const Topo &t, int head_rows, const HeadWgJob *head_job, LossHook &&loss_on_side) {
+    Ctx &c = b.c;
+    const ImkLayer &ol = c.p->layers[t.out];
+    int rc;
+#define OK(e) do { rc = (e); if (rc) return rc; } while (0)
+    b.dy_rows[t.d_bnb[3]] = head_rows;
+    if (head_job)
+        OK(imk_wgf_add_job(b.jobs, head_job->partial, head_job->rows, ol.ksize, ol.cin, ol.cout, b.grads + ol.off_w, b.grads + ol.off_b));
+    // decoders 9..6
+    for (int j = 3; j >= 0; --j) {
+        f16 *dU = reinterpret_cast<f16 *>(c.base + c.ws.dU[j]);
+        if (j == 3) OK(b.bn_bwd(t.d_bnb[j], 0, nullptr, nullptr));
+        else OK(b.bn_bwd(t.d_bnb[j], 2, nullptr, reinterpret_cast<f16 *>(c.base + c.ws.dU[j + 1])));
+        OK(b.wgrad_dgrad(t.d_c1[j], c.dA(t.d_c3[j]), c.act(t.d_c3[j])));
+        OK(b.wgrad_dgrad(t.d_c3[j], c.dy(t.d_bna[j]), nullptr, t.d_bna[j]));
+        OK(b.bn_bwd(t.d_bna[j], 0, nullptr, nullptr));
+        b.sum2_bn = j > 0 ? t.d_bnb[j - 1] : t.b_bn;     // dU's 2x2 sums = dy of the block below: assembled by this dgrad where it can
+        OK(b.wgrad_dgrad(t.d_ca[j], dU, nullptr));
+        OK(b.flush_block());    // the block's weight gradients (and the head's, for the first block) -> side stream
+        OK(loss_on_side());
+    }
+    // bottleneck: dy = 2x2 sum of dU[decoder 6]
+    OK(b.bn_bwd(t.b_bn, 2, nullptr, reinterpret_cast<f16 *>(c.base + c.ws.dU[0])));
+    OK(b.wgrad_dgrad(t.b_c1, c.dA(t.b_c3), c.act(t.b_c3)));
+    OK(b.wgrad_dgrad(t.b_c3, reinterpret_cast<f16 *>(c.base + c.ws.dP[3]), nullptr));
+    OK(b.flush_block());
+    // encoders 4..1: dy = skip gradient (dU of decoder 6+(3-i)) + max-pool scatter of dP[i]
+    for (int i = 3; i >= 0; --i) {
+        if (i == 0) {
+            b.defer_finalize = true;   // last block: nothing left to hide its split reductions behind
+            b.hold_conv = t.e_c3[0];
+        }
+        OK(b.bn_bwd(t.e_bn[i], 1, reinterpret_cast<f16 *>(c.base + c.ws.dU[3 - i]),
+                    reinterpret_cast<f16 *>(c.base + c.ws.dP[i])));
+        OK(b.wgrad_dgrad(t.e_c1[i], c.dA(t.e_c3[i]), c.act(t.e_c3[i])));
+        f16 *dst = i > 0 ? reinterpret_cast<f16 *>(c.base + c.ws.dP[i - 1]) : c.dy(t.in_bn);
+        OK(b.wgrad_dgrad(t.e_c3[i], dst, nullptr, i > 0 ? -1 : t.in_bn));
+        OK(i > 0 ? b.flush_block() : b.flush_wgrads());
+    }
+    OK(b.bn_bwd(t.in_bn, 0, nullptr, nullptr));
+    if (b.has_held) {
+        OK(b.wgrad(t.in_c));                        // full resolution: forked onto the side stream at once
+        b.pending[b.n_pending++] = b.held;          // launched on the main stream by finish_wgrads
+    } else {
+        OK(b.wgrad(t.in_c, nullptr, true));
+    }
+    OK(b.finish_wgrads());
+#undef OK
+    return IMK_OK;
+}
+
+}  // namespace
+
 extern "C" int imk_unet_fwd_bwd(const imk_unet_plan *plan, float *params, void *packed, void *state, const uint8_t *x,
                                 const uint8_t *y, int batch, int loss_kind, float *grads, float *stats, void *workspace,
                                 int64_t workspace_bytes, void *stream_) {
@@ -671,91 +775,138 @@ extern "C" int imk_unet_fwd_bwd(const imk_unet_plan *plan, float *params, void *
         loss_done = true;
         return imk_launch_loss_finalize(loss_partial, n_pix, cf.n_out, loss_kind, stats, plan->side[(b.n_fork - 1) % b.n_side]);
     };
+    int head_rows = 0;
+    HeadWgJob head_job{};
     if (head_mse_pass) {
         const int rows = imk_head_cce_fused_rows(n_pix);
         float *wgp = reinterpret_cast<float *>(c.base + c.ws.L[t.out].wg_partial);
         OK(imk_launch_head_mse_fused(c.act(t.d_c1[3]), c.bn_scale(obn), c.bn_shift(obn), params + ol.off_w, params + ol.off_b,
                                      ol.cin, imk_pad8(ol.cin), ol.cout, n_pix, y, sv.ctl, stats, c.dy(obn), loss_partial,
                                      reinterpret_cast<float *>(c.base + c.ws.L[obn].bwd_partial), wgp, stream));
-        b.dy_rows[obn] = rows;
-        OK(imk_wgf_add_job(b.jobs, wgp, rows, ol.ksize, ol.cin, ol.cout, grads + ol.off_w, grads + ol.off_b));
+        head_rows = rows;
+        head_job = HeadWgJob{wgp, rows};
     } else if (head_one_pass) {
         const int rows = imk_head_cce_fused_rows(n_pix);
         float *wgp = reinterpret_cast<float *>(c.base + c.ws.L[t.out].wg_partial);
         OK(imk_launch_head_cce_fused(c.act(t.d_c1[3]), c.bn_scale(obn), c.bn_shift(obn), params + ol.off_w, params + ol.off_b,
                                      ol.cin, imk_pad8(ol.cin), ol.cout, n_pix, y, sv.ctl, stats, c.dy(obn), loss_partial,
                                      reinterpret_cast<float *>(c.base + c.ws.L[obn].bwd_partial), wgp, stream));
-        b.dy_rows[obn] = rows;
-        OK(imk_wgf_add_job(b.jobs, wgp, rows, ol.ksize, ol.cin, ol.cout, grads + ol.off_w, grads + ol.off_b));
+        head_rows = rows;
+        head_job = HeadWgJob{wgp, rows};
     } else {
-        // head: its "dA" is dlogit.  Its dgrad (dlogit -> dy of the last BatchNorm, with that BN's gradient statistics) reads
-        // exactly the operands of its weight gradient (dlogit, and z = the last decoder activation, whose BatchNorm output is
-        // the head's input): where the pipelined kernel covers the shape, one launch produces both.
-        ImkConvArgs ha{};
-        ha.x.in = dlogit; ha.x.lmode = LM_RAW; ha.x.cin = ol.cout; ha.x.cs_in = imk_pad8(ol.cout);
-        ha.B = batch; ha.H = cf.h; ha.W = cf.w; ha.ksize = 1; ha.cout = ol.cin; ha.cs_out = imk_pad8(ol.cin);
-        ha.wpk = c.wbwd(t.out); ha.out = c.dy(obn); ha.epi = EP_PLAIN;
-        ha.dystat_z = c.act(t.d_c1[3]);
-        ha.stats_partial = reinterpret_cast<float *>(c.base + c.ws.L[obn].bwd_partial);
-        const bool head_fused = imk_conv_can_fuse_wgrad(ha);
-        if (!head_fused) OK(b.wgrad(t.out, dlogit));
-        // the loss value only needs head_loss_kernel's partials: its reduction rides on the side stream, behind the head's
-        // weight gradient, instead of sitting at the end of the step
-        OK(loss_on_side());
-        int rows = 0;
-        ha.stats_rows = &rows;
-        if (head_fused) {
-            ha.wg_partial = reinterpret_cast<float *>(c.base + c.ws.L[t.out].wg_partial);
-            ha.wg_sc = c.bn_scale(obn); ha.wg_sh = c.bn_shift(obn);
-        }
-        OK(imk_launch_conv(ha, stream));
-        if (rows <= 0 || rows > c.ws.L[obn].n_bwd_rows) return IMK_EWORKSPACE;
-        b.dy_rows[obn] = rows;
-        if (head_fused) {
-            if (rows > imk_conv_fused_wgrad_rows_max()) return IMK_EWORKSPACE;
-            OK(imk_wgf_add_job(b.jobs, ha.wg_partial, rows, ol.ksize, ol.cin, ol.cout, grads + ol.off_w, grads + ol.off_b));
-        }
+        OK(head_dgrad(b, t, dlogit, loss_on_side, &head_rows, &head_job));
     }
-    // decoders 9..6
-    for (int j = 3; j >= 0; --j) {
-        f16 *dU = reinterpret_cast<f16 *>(c.base + c.ws.dU[j]);
-        if (j == 3) OK(b.bn_bwd(t.d_bnb[j], 0, nullptr, nullptr));
-        else OK(b.bn_bwd(t.d_bnb[j], 2, nullptr, reinterpret_cast<f16 *>(c.base + c.ws.dU[j + 1])));
-        OK(b.wgrad_dgrad(t.d_c1[j], c.dA(t.d_c3[j]), c.act(t.d_c3[j])));
-        OK(b.wgrad_dgrad(t.d_c3[j], c.dy(t.d_bna[j]), nullptr, t.d_bna[j]));
-        OK(b.bn_bwd(t.d_bna[j], 0, nullptr, nullptr));
-        b.sum2_bn = j > 0 ? t.d_bnb[j - 1] : t.b_bn;     // dU's 2x2 sums = dy of the block below: assembled by this dgrad where it can
-        OK(b.wgrad_dgrad(t.d_ca[j], dU, nullptr));
-        OK(b.flush_block());    // the block's weight gradients (and the head's, for the first block) -> side stream
-        OK(loss_on_side());
-    }
-    // bottleneck: dy = 2x2 sum of dU[decoder 6]
-    OK(b.bn_bwd(t.b_bn, 2, nullptr, reinterpret_cast<f16 *>(c.base + c.ws.dU[0])));
-    OK(b.wgrad_dgrad(t.b_c1, c.dA(t.b_c3), c.act(t.b_c3)));
-    OK(b.wgrad_dgrad(t.b_c3, reinterpret_cast<f16 *>(c.base + c.ws.dP[3]), nullptr));
-    OK(b.flush_block());
-    // encoders 4..1: dy = skip gradient (dU of decoder 6+(3-i)) + max-pool scatter of dP[i]
-    for (int i = 3; i >= 0; --i) {
-        if (i == 0) {
-            b.defer_finalize = true;   // last block: nothing left to hide its split reductions behind
-            b.hold_conv = t.e_c3[0];
-        }
-        OK(b.bn_bwd(t.e_bn[i], 1, reinterpret_cast<f16 *>(c.base + c.ws.dU[3 - i]),
-                    reinterpret_cast<f16 *>(c.base + c.ws.dP[i])));
-        OK(b.wgrad_dgrad(t.e_c1[i], c.dA(t.e_c3[i]), c.act(t.e_c3[i])));
-        f16 *dst = i > 0 ? reinterpret_cast<f16 *>(c.base + c.ws.dP[i - 1]) : c.dy(t.in_bn);
-        OK(b.wgrad_dgrad(t.e_c3[i], dst, nullptr, i > 0 ? -1 : t.in_bn));
-        OK(i > 0 ? b.flush_block() : b.flush_wgrads());
-    }
-    OK(b.bn_bwd(t.in_bn, 0, nullptr, nullptr));
-    if (b.has_held) {
-        OK(b.wgrad(t.in_c));                        // full resolution: forked onto the side stream at once
-        b.pending[b.n_pending++] = b.held;          // launched on the main stream by finish_wgrads
-    } else {
-        OK(b.wgrad(t.in_c, nullptr, true));
-    }
-    OK(b.finish_wgrads());
+    OK(run_backward(b, t, head_rows, head_job.partial ? &head_job : nullptr, loss_on_side));
     if (!loss_done) OK(imk_launch_loss_finalize(loss_partial, n_pix, cf.n_out, loss_kind, stats, stream));
+#undef OK
+    return IMK_OK;
+}
+
+// Consistency-loss step (functions.py:367-474 of the reference): two training-mode forwards on two views of one unlabelled batch,
+// L = mean (p1 - p2)^2, the gradient through both forwards.  Workspace: [view 1's training workspace | view 2's | the second
+// gradient vector | the head's loss partials]; the fused head's weight-gradient rows (both views in one set) take the output layer's
+// own partial buffer in view 1's workspace, which is sized for one row per head workgroup plus the reduction's scratch behind them.
+// Everything runs in order on `stream` (the weight gradients inside each backward pass fork to the side stream as in the labelled step).
+namespace {
+struct ConsistLayout {
+    Ws ws;
+    size_t view[2], grads2, loss_partial, total;
+};
+ConsistLayout consist_layout(const imk_unet_plan *plan, int batch) {
+    ConsistLayout l{make_ws(plan, batch, 1), {0, 0}, 0, 0, 0};
+    const int rows = imk_loss_blocks((long long)batch * plan->cfg.h * plan->cfg.w);
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off = up(off + bytes); return o; };
+    l.view[0] = take(l.ws.total);
+    l.view[1] = take(l.ws.total);
+    l.grads2 = take((size_t)plan->n_trainable * sizeof(float));
+    l.loss_partial = take((size_t)rows * sizeof(float));
+    l.total = off;
+    return l;
+}
+}  // namespace
+
+extern "C" int64_t imk_unet_consistency_workspace_bytes(const imk_unet_plan *plan, int batch) {
+    if (!plan || plan->net != 0 || batch <= 0) return IMK_EINVAL;
+    return (int64_t)consist_layout(plan, batch).total;
+}
+
+extern "C" int imk_unet_consistency_fwd_bwd(const imk_unet_plan *plan, float *params, void *packed, void *state,
+                                            const uint8_t *x1, const uint8_t *x2, int batch, float *grads, float *stats,
+                                            void *workspace, int64_t workspace_bytes, void *stream_) {
+    IMK_CHECK_ARG(plan && plan->net == 0 && params && packed && state && x1 && x2 && grads && stats && workspace && batch > 0);
+    const ConsistLayout lay = consist_layout(plan, batch);
+    if ((int64_t)lay.total > workspace_bytes) return IMK_EWORKSPACE;
+    hipStream_t stream = (hipStream_t)stream_;
+    uint8_t *base = (uint8_t *)workspace;
+    Ctx c1{plan, lay.ws, base + lay.view[0], params, (const uint8_t *)packed, batch, true, stream};
+    Ctx c2{plan, lay.ws, base + lay.view[1], params, (const uint8_t *)packed, batch, true, stream};
+    c1.x_in[0] = x1;
+    c2.x_in[0] = x2;
+    const StateView sv = state_view(plan, state);
+    const imk_unet_cfg &cf = plan->cfg;
+    const Topo t = make_topo(plan);
+    const long long n_pix = (long long)batch * cf.h * cf.w;
+    const ImkLayer &ol = plan->layers[t.out];
+    const int obn = t.d_bnb[3], cs = imk_pad8(ol.cin);
+    float *grads2 = reinterpret_cast<float *>(base + lay.grads2);
+    float *loss_partial = reinterpret_cast<float *>(base + lay.loss_partial);
+    int rc;
+#define OK(e) do { rc = (e); if (rc) return rc; } while (0)
+    // both forwards with batch statistics; each BatchNorm's finalize moves the moving statistics, view 1 first
+    OK(run_forward(c1, t, nullptr, params));
+    OK(run_forward(c2, t, nullptr, params));
+
+    // the fused head's weight-gradient rows carry both views and are reduced into `grads` alone: the output layer is the last entry
+    // of the trainable section, and the final sum then stops in front of it
+    const bool fused = !plan->dbg_materialize && imk_switches().consistency_fused &&
+                       ol.off_b + ol.cout == plan->n_trainable &&
+                       imk_consistency_fused_ok(cs, ol.cout, cf.act_out, n_pix, lay.ws.L[obn].n_bwd_rows);
+    const int head_rows = imk_loss_blocks(n_pix);
+    HeadWgJob fused_job{reinterpret_cast<float *>(c1.base + lay.ws.L[t.out].wg_partial), head_rows};
+    f16 *dlogit1 = reinterpret_cast<f16 *>(c1.base + lay.ws.dlogit), *dlogit2 = reinterpret_cast<f16 *>(c2.base + lay.ws.dlogit);
+    if (fused) {
+        OK(imk_launch_consistency_head(c1.act(t.d_c1[3]), c2.act(t.d_c1[3]), c1.bn_scale(obn), c1.bn_shift(obn), c2.bn_scale(obn),
+                                       c2.bn_shift(obn), params + ol.off_w, params + ol.off_b, ol.cin, cs, ol.cout, n_pix, sv.ctl,
+                                       stats, c1.dy(obn), c2.dy(obn), loss_partial,
+                                       reinterpret_cast<float *>(c1.base + lay.ws.L[obn].bwd_partial),
+                                       reinterpret_cast<float *>(c2.base + lay.ws.L[obn].bwd_partial), fused_job.partial, stream));
+    } else {
+        float *p1 = reinterpret_cast<float *>(c1.base + lay.ws.probs), *p2 = reinterpret_cast<float *>(c2.base + lay.ws.probs);
+        OK(imk_launch_head(c1.act(t.d_c1[3]), c1.bn_scale(obn), c1.bn_shift(obn), params + ol.off_w, params + ol.off_b, ol.cin, cs,
+                           ol.cout, cf.act_out, n_pix, p1, stream));
+        OK(imk_launch_head(c2.act(t.d_c1[3]), c2.bn_scale(obn), c2.bn_shift(obn), params + ol.off_w, params + ol.off_b, ol.cin, cs,
+                           ol.cout, cf.act_out, n_pix, p2, stream));
+        OK(imk_launch_consistency_dlogit(p1, p2, ol.cout, cf.act_out, n_pix, sv.ctl, stats, dlogit1, dlogit2, loss_partial, stream));
+    }
+
+    const int n_side = imk_switches().side_streams;
+    const bool side_on = !plan->dbg_single_stream && n_side > 0 && ensure_side_streams(plan, n_side);
+    {   // backward of view 1 into `grads`; the loss value rides on its first fork, as in the labelled step
+        Bwd b{c1, grads, sv.ctl, stats + 1, side_on ? n_side : 0};
+        ImkStopRingScope stop_ring(plan, stream, b.n_side);
+        bool loss_done = false;
+        auto loss_on_side = [&]() -> int {
+            if (loss_done || b.n_side <= 0 || b.n_fork <= 0) return IMK_OK;
+            loss_done = true;
+            return imk_launch_loss_finalize(loss_partial, n_pix, cf.n_out, 0, stats, plan->side[(b.n_fork - 1) % b.n_side]);
+        };
+        int rows = head_rows;
+        HeadWgJob job = fused ? fused_job : HeadWgJob{};
+        if (!fused) OK(head_dgrad(b, t, dlogit1, loss_on_side, &rows, &job));
+        OK(run_backward(b, t, rows, job.partial ? &job : nullptr, loss_on_side));
+        if (!loss_done) OK(imk_launch_loss_finalize(loss_partial, n_pix, cf.n_out, 0, stats, stream));
+    }
+    {   // backward of view 2 into the second vector
+        Bwd b{c2, grads2, sv.ctl, stats + 1, side_on ? n_side : 0};
+        ImkStopRingScope stop_ring(plan, stream, b.n_side);
+        auto no_loss = []() -> int { return IMK_OK; };
+        int rows = head_rows;
+        HeadWgJob job{};
+        if (!fused) OK(head_dgrad(b, t, dlogit2, no_loss, &rows, &job));
+        OK(run_backward(b, t, rows, job.partial ? &job : nullptr, no_loss));
+    }
+    OK(imk_launch_grad_add(grads, grads2, fused ? ol.off_w : plan->n_trainable, stats + 1, stream));
 #undef OK
     return IMK_OK;
 }

@@ -1877,3 +1877,5 @@ from .evalnet_functions import (compute_classwise_detection, compute_classwise_d
                                 create_training_data_for_segnet_with_miou_ensemble_multiclass, load_evalnet, num_augs_from_miou,
                                 save_evalnet, train_evalnet_ISIC_2018, train_evalnet_miou_model_hela,
                                 train_evalnet_miou_model_multiclass)
+from .consistency import (train_hela_consistency_loss, train_ISIC_2018_consistency_loss,  # noqa: E402,F401
+                          train_multiclass_consistency_loss)

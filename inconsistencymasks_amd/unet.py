@@ -231,15 +231,21 @@ class UNet:
             outs.append(self.predict_device(xt[i:i + batch_size]))
         return torch.cat(outs, 0).cpu().numpy()
 
-    def intermediate(self, layer_name, batch, mode=0, which=0):
-        """Debug/parity: a stored intermediate after the last forward (fp16 -> float32 CPU [B,h,w,c])."""
+    def intermediate(self, layer_name, batch, mode=0, which=0, view=None):
+        """Debug/parity: a stored intermediate after the last forward (fp16 -> float32 CPU [B,h,w,c]).
+        view=0|1: of that view's forward inside the two-view workspace of the last consistency_fwd_bwd (mode 1)."""
         idx = [l["name"] for l in self.plan.layers].index(layer_name)
         off, h, w, c, cs = ctypes.c_int64(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
         check(lib.imk_unet_tensor_info(self.plan.ptr, batch, mode, idx, which, ctypes.byref(off), ctypes.byref(h),
                                        ctypes.byref(w), ctypes.byref(c), ctypes.byref(cs)), "imk_unet_tensor_info")
-        ws = [v for k, v in self._ws.items() if k[0] == batch and k[1] == mode][0]
+        if view is None:
+            ws, base = [v for k, v in self._ws.items() if k[0] == batch and k[1] == mode][0], off.value
+        else:
+            if mode != 1 or view not in (0, 1):
+                raise ValueError("view=0|1 reads the two-view training workspace (mode=1)")
+            ws, base = self._ws[(batch, "consistency", 0)], view * self.plan.workspace_bytes(batch, 1) + off.value
         n = batch * h.value * w.value * cs.value
-        t = ws[off.value:off.value + 2 * n].view(torch.float16).reshape(batch, h.value, w.value, cs.value)
+        t = ws[base:base + 2 * n].view(torch.float16).reshape(batch, h.value, w.value, cs.value)
         return t[..., :c.value].float().cpu()
 
     # ---- training ---------------------------------------------------------------------------------------
@@ -264,6 +270,37 @@ class UNet:
                                    self.train_state.data_ptr(), x_u8.data_ptr(), y_u8.data_ptr(), b, int(loss_kind),
                                    self.grads.data_ptr(), self.stats.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
               "imk_unet_fwd_bwd")
+
+    def consistency_workspace(self, batch):
+        key = (batch, "consistency", 0)
+        if key not in self._ws:
+            self._ws = {k: v for k, v in self._ws.items() if k[1] != "consistency"}
+            n = lib.imk_unet_consistency_workspace_bytes(self.plan.ptr, batch)
+            if n < 0:
+                check(int(n), "imk_unet_consistency_workspace_bytes")
+            self._ws[key] = torch.empty(n, dtype=torch.uint8, device=self.device)
+        return self._ws[key]
+
+    def consistency_fwd_bwd(self, x1_u8, x2_u8):
+        """Forward/backward of the consistency loss mean((model(x1) - model(x2))^2) on two views of one unlabelled batch, both
+        forwards in training mode; fills self.grads (unscaled) and self.stats like fwd_bwd."""
+        if x1_u8.shape != x2_u8.shape:
+            raise ValueError(f"the two views differ in shape: {tuple(x1_u8.shape)} vs {tuple(x2_u8.shape)}")
+        if self.train_state is None:
+            self.init_train_state()
+        if not self._packed_ok:
+            self.repack()
+        self._fold_ok = False        # both forwards update the moving statistics
+        b = x1_u8.shape[0]
+        ws = self.consistency_workspace(b)
+        check(lib.imk_unet_consistency_fwd_bwd(self.plan.ptr, self.params.data_ptr(), self.packed.data_ptr(),
+                                               self.train_state.data_ptr(), x1_u8.data_ptr(), x2_u8.data_ptr(), b,
+                                               self.grads.data_ptr(), self.stats.data_ptr(), ws.data_ptr(), ws.numel(), _stream()),
+              "imk_unet_consistency_fwd_bwd")
+
+    def consistency_step(self, x1_u8, x2_u8, lr, wd):
+        self.consistency_fwd_bwd(x1_u8, x2_u8)
+        self.adamw_step(lr, wd)
 
     def adamw_step(self, lr, wd, grad_scale=1.0, beta1=0.9, beta2=0.999, eps=1e-7):
         check(lib.imk_unet_adamw_step(self.plan.ptr, self.params.data_ptr(), self.packed.data_ptr(),
