@@ -1,0 +1,11 @@
+"""SUIM full-dataset baseline (the upper bound) on MI355X: counterpart of the reference driver SUIM/03_SUIM_full_dataset.py
+(same loops, file / model / CSV names); the loop body lives in inconsistencymasks_amd/subset_driver.py."""
+import os
+import sys
+
+sys.path.append(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+from inconsistencymasks_amd.subset_driver import run  # noqa: E402
+
+if __name__ == "__main__":
+    run("SUIM", full=True)

@@ -440,13 +440,15 @@ IMK_API int imk_evalnet_tensor_info(const imk_unet_plan *plan, int batch, int mo
 
 /* ------------------------------------------------------------------------------------------------
  * EvalNet-ensemble selection baseline (create_training_data_for_segnet_with_ensemble_binary,
- * ..._with_miou_ensemble_hela, ..._with_miou_ensemble_multiclass: functions.py:5070-5155, 5323-5577)
+ * ..._with_miou_ensemble_hela, ..._with_miou_ensemble_multiclass: functions.py:5070-5155, 5323-5577) and the single-EvalNet
+ * baseline (create_training_data_for_segnet_ISIC_2018, :4991-5063 = IMK_SELECT_IOU with N = 1;
+ * create_training_data_by_evalnet_miou_for_segnet_multiclass, :5583-5677 = IMK_SELECT_CONF_GATED)
  * ----------------------------------------------------------------------------------------------
  * For every unlabeled image the reference stacks M candidate masks, scores the (image, mask) pairs with the N EvalNets of the
  * ensemble, averages over the EvalNets, takes the arg-max candidate and keeps the pair if its score reaches a threshold.  */
 #define IMK_SELECT_MAX_CAND 16    /* candidates per image */
 #define IMK_SELECT_MAX_MODELS 8   /* EvalNets per ensemble */
-enum { IMK_SELECT_IOU = 0, IMK_SELECT_MIOU = 1 };
+enum { IMK_SELECT_IOU = 0, IMK_SELECT_MIOU = 1, IMK_SELECT_CONF_GATED = 2 };
 
 /* The selection rule and the gather of the chosen candidate, one kernel.
  *   scores     [N,B,M,n_heads*n_out] f32, unit order of imk_evalnet_forward (iou units first, then detection units)
@@ -461,6 +463,14 @@ enum { IMK_SELECT_IOU = 0, IMK_SELECT_MIOU = 1 };
  *   IMK_SELECT_MIOU (n_heads = 2): class k counts if its mean detection >= 0.5f (NaN does not); score = the fp32 sum of the counting
  *                   classes' mean ious in class order (the first addend as it is), divided by their number (correctly rounded);
  *                   0 if no class counts.
+ *   IMK_SELECT_CONF_GATED (n_heads = 2): the rule of the single-EvalNet writer create_training_data_by_evalnet_miou_for_segnet_multiclass
+ *                   (functions.py:5649-5672; the reference runs it with N = 1, where the mean over the models is the value itself).
+ *                   Gate: g_k = the fp32 sum of class k's mean detection over the image's candidates m = 0 .. cnt-1 in candidate order,
+ *                   divided by cnt (correctly rounded) -- np.mean(axis=0) of the float32 [M,K]; class k counts, for every candidate of
+ *                   the image, iff g_k >= 0.03f (NaN does not).  cnt = counts[b], or M.  Score of candidate m = the fp32 sum of its
+ *                   mean DETECTION values over the counting classes in class order (the first addend as it is), divided by their
+ *                   number (correctly rounded); 0 if no class counts.  The iou units (the first K of every row) are read by nobody
+ *                   in this mode, as in the reference.  Its own kernel; modes 0 and 1 run the code they ran before.
  * best_idx = np.argmax of the scores (the first maximum; the first NaN wins); keep = best >= (float)thr (NaN keeps nothing): numpy
  * compares the float32 score with the Python threshold in float32.
  * N > IMK_SELECT_MAX_MODELS or M > IMK_SELECT_MAX_CAND (or n_out > 64): IMK_EUNSUPPORTED, before any launch.               */

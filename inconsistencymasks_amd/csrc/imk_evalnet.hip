@@ -272,7 +272,7 @@ extern "C" int imk_evalnet_forward_select(const imk_unet_plan *plan, int n_model
                             imk_switches().select_shared);
     if (rc) return rc;
     const ImkSelectArgs a{scores, counts, cand, n_models, batch, n_cand, n_heads, e.n_out, mode == IMK_SELECT_MIOU, cand_bytes,
-                          (float)thr, best_idx, best_score, keep, out};
+                          (float)thr, best_idx, best_score, keep, out, mode == IMK_SELECT_CONF_GATED};
     return imk_launch_evalnet_select(a, stream);
 }
 

@@ -206,6 +206,7 @@ struct ImkSelectArgs {
     int32_t *best_idx;
     float *best_score;
     uint8_t *keep, *out;
+    int gated;              // IMK_SELECT_CONF_GATED: evalnet_select_gated_kernel (n_heads == 2, `miou` unused)
 };
 int imk_launch_evalnet_select(const ImkSelectArgs &a, hipStream_t stream);
 // imk_evalnet_select's argument rules (limits, alignment, a read-back of `counts` when given): IMK_OK or the call's error code

@@ -5,6 +5,11 @@
 //   IMK_SELECT_IOU             score = that mean of the single unit
 //   IMK_SELECT_MIOU            classes whose mean detection is >= 0.5f count; score = their mean ious summed in class order (Python's
 //                              sum() over np.float32: the first addend as it is), divided by their number; 0.0 if none counts
+//   IMK_SELECT_CONF_GATED      the single-EvalNet rule of create_training_data_by_evalnet_miou_for_segnet_multiclass (:5649-5672): class k
+//                              counts for every candidate of the image if the mean of its detection values over the image's candidates
+//                              (summed in candidate order, one divide: np.mean(axis=0) of the float32 [M,K]) is >= 0.03f; score = the
+//                              candidate's detection values of the counting classes summed in class order, divided by their number;
+//                              0.0 if none counts.  The iou units are not read.  A kernel of its own (evalnet_select_gated_kernel).
 //   best                       np.argmax: the first maximum wins, the first NaN wins;  keep = best >= (float)thr (NaN: no)
 // One workgroup per (16 KB chunk of the candidate, image): every workgroup of an image evaluates the rule itself -- at most
 // N * M * units = 8 * 16 * 128 floats, cache hits after the first -- and copies its chunk of the winner with 16-byte accesses.
@@ -82,6 +87,68 @@ __global__ __launch_bounds__(256) void evalnet_select_kernel(ImkSelectArgs a) {
     for (int j = 0; j < SEL_VEC_PER_THREAD; ++j) if (v0 + j * 256 < n_vec) dst[v0 + j * 256] = r[j];
 }
 
+// IMK_SELECT_CONF_GATED: as above, with one reduction across the candidates of the image (the gate) between the means over the
+// models and the scores.  Reads the detection units only.
+__global__ __launch_bounds__(256) void evalnet_select_gated_kernel(ImkSelectArgs a) {
+    __shared__ float s_det[IMK_SELECT_MAX_CAND * SEL_MAX_OUT];
+    __shared__ float s_gate[SEL_MAX_OUT];
+    __shared__ float s_score[IMK_SELECT_MAX_CAND];
+    __shared__ int s_best;
+    const int b = blockIdx.y, t = threadIdx.x;
+    const int M = a.n_cand, K = a.n_out, U = 2 * K, N = a.n_models;
+    int cnt = a.counts ? a.counts[b] : M;
+    cnt = cnt < 1 ? 1 : (cnt > M ? M : cnt);                  // the host refuses such counts; never index outside the image's rows
+    const float fn = (float)N;
+    const size_t model_stride = (size_t)a.batch * M * U;
+    const float *sb = a.scores + (size_t)b * M * U + K;       // the detection units follow the K iou units
+    for (int i = t; i < cnt * K; i += 256) {                  // (candidate, class): the means over the models, in model order
+        const int m = i / K, k = i - m * K;
+        const float *p = sb + (size_t)m * U + k;
+        float sd = p[0];
+        for (int n = 1; n < N; ++n) sd += p[n * model_stride];
+        s_det[i] = __fdiv_rn(sd, fn);
+    }
+    __syncthreads();
+    if (t < K) {                                              // the gate: the class's mean over the image's candidates, in candidate order
+        float g = s_det[t];
+        for (int m = 1; m < cnt; ++m) g += s_det[m * K + t];
+        s_gate[t] = __fdiv_rn(g, (float)cnt);
+    }
+    __syncthreads();
+    if (t < cnt) {
+        float s = 0.f;
+        int c = 0;
+        for (int k = 0; k < K; ++k)
+            if (s_gate[k] >= 0.03f) {                         // NaN compares false
+                s = c ? s + s_det[t * K + k] : s_det[t * K + k];
+                ++c;
+            }
+        s_score[t] = c ? __fdiv_rn(s, (float)c) : 0.f;
+    }
+    __syncthreads();
+    if (t == 0) {
+        float bv = 0.f;
+        int bk = -1;
+        for (int m = 0; m < cnt; ++m) np_argmax_step(s_score[m], m, bv, bk);
+        s_best = bk;
+        if (blockIdx.x == 0) {
+            a.best_idx[b] = bk;
+            a.best_score[b] = bv;
+            a.keep[b] = bv >= a.thr ? 1 : 0;                  // NaN compares false
+        }
+    }
+    __syncthreads();
+    const long long n_vec = a.cand_bytes / 16;
+    const uint4 *src = reinterpret_cast<const uint4 *>(a.cand + ((size_t)b * M + s_best) * a.cand_bytes);
+    uint4 *dst = reinterpret_cast<uint4 *>(a.out + (size_t)b * a.cand_bytes);
+    const long long v0 = (long long)blockIdx.x * SEL_CHUNK_VECS + t;
+    uint4 r[SEL_VEC_PER_THREAD];
+#pragma unroll
+    for (int j = 0; j < SEL_VEC_PER_THREAD; ++j) if (v0 + j * 256 < n_vec) r[j] = src[v0 + j * 256];
+#pragma unroll
+    for (int j = 0; j < SEL_VEC_PER_THREAD; ++j) if (v0 + j * 256 < n_vec) dst[v0 + j * 256] = r[j];
+}
+
 // [B][n_vec] -> [B][n_rep][n_vec]: one load, n_rep stores per vector
 template <typename V>
 __global__ __launch_bounds__(256) void repeat_rows_kernel(const V *__restrict__ src, long long n_vec, int n_rep, V *__restrict__ dst) {
@@ -100,7 +167,8 @@ int imk_launch_evalnet_select(const ImkSelectArgs &a, hipStream_t stream) {
     const long long n_vec = a.cand_bytes / 16;
     const dim3 grid((unsigned)((n_vec + SEL_CHUNK_VECS - 1) / SEL_CHUNK_VECS), a.batch);
     ImkProfScope prof(PF_IM, (double)a.batch * (2.0 * a.cand_bytes + 4.0 * a.n_models * a.n_cand * a.n_heads * a.n_out), stream);
-    imk_klaunch(evalnet_select_kernel, grid, dim3(256), 0, stream, a);
+    if (a.gated) imk_klaunch(evalnet_select_gated_kernel, grid, dim3(256), 0, stream, a);
+    else imk_klaunch(evalnet_select_kernel, grid, dim3(256), 0, stream, a);
     IMK_LAUNCH_CHECK();
     return IMK_OK;
 }
@@ -125,7 +193,7 @@ int imk_launch_repeat_rows(const uint8_t *src, int batch, int n_rep, long long r
 int imk_select_check(int n_models, int batch, int n_cand, int n_heads, int n_out, const int32_t *counts, const uint8_t *cand,
                      int64_t cand_bytes, int mode, const uint8_t *out, hipStream_t stream) {
     IMK_CHECK_ARG(n_models > 0 && batch > 0 && n_cand > 0 && n_out > 0 && cand && out);
-    IMK_CHECK_ARG(mode == IMK_SELECT_IOU || mode == IMK_SELECT_MIOU);
+    IMK_CHECK_ARG(mode == IMK_SELECT_IOU || mode == IMK_SELECT_MIOU || mode == IMK_SELECT_CONF_GATED);
     IMK_CHECK_ARG(mode == IMK_SELECT_IOU ? (n_heads == 1 && n_out == 1) : n_heads == 2);
     IMK_CHECK_ARG(cand_bytes > 0 && cand_bytes % 16 == 0 && aligned16(cand) && aligned16(out));
     if (n_models > IMK_SELECT_MAX_MODELS || n_cand > IMK_SELECT_MAX_CAND || n_out > SEL_MAX_OUT || batch > 65535) return IMK_EUNSUPPORTED;
@@ -146,6 +214,6 @@ extern "C" int imk_evalnet_select(const float *scores, int n_models, int batch, 
     int rc = imk_select_check(n_models, batch, n_cand, n_heads, n_out, counts, cand, cand_bytes, mode, out, stream);
     if (rc) return rc;
     const ImkSelectArgs a{scores, counts, cand, n_models, batch, n_cand, n_heads, n_out, mode == IMK_SELECT_MIOU, cand_bytes,
-                          (float)thr, best_idx, best_score, keep, out};
+                          (float)thr, best_idx, best_score, keep, out, mode == IMK_SELECT_CONF_GATED};
     return imk_launch_evalnet_select(a, stream);
 }

@@ -119,7 +119,7 @@ class EvalNet(UNet):
 
 
 # ---- EvalNet-ensemble selection (imk_evalnet_select / imk_evalnet_forward_select, include/imk.h) -----------------------------
-SELECT_IOU, SELECT_MIOU = 0, 1
+SELECT_IOU, SELECT_MIOU, SELECT_CONF_GATED = 0, 1, 2
 SELECT_MAX_CAND, SELECT_MAX_MODELS = 16, 8
 
 
@@ -139,13 +139,15 @@ def select_candidates(scores, cand, thr, mode, counts=None):
     """scores float32 [N,B,M,U] (device; U = 1, or the iou units then the detection units), cand uint8 [B,M,...] (device; a multiple
     of 16 bytes per candidate), counts int32 [B] (device) or None -> (best_idx [B] i32, best_score [B] f32, keep [B] u8, out [B,...] u8):
     the arg-max candidate by the ensemble's mean IoU (SELECT_IOU) or mean mIoU over the detected classes (SELECT_MIOU), kept where the
-    score reaches thr -- the rule of the reference's create_training_data_for_segnet_with_*ensemble* writers."""
+    score reaches thr -- the rule of the reference's create_training_data_for_segnet_with_*ensemble* writers.  SELECT_CONF_GATED is the
+    single-EvalNet multi-class writer's rule: the mean detection value over the classes whose mean detection over the image's
+    candidates reaches 0.03 (create_training_data_by_evalnet_miou_for_segnet_multiclass); the iou units are not read."""
     if scores.dtype != torch.float32 or scores.dim() != 4 or not scores.is_cuda:
         raise TypeError("scores must be a float32 CUDA tensor [N,B,M,U]")
     scores, cand = scores.contiguous(), cand.contiguous()
     n, b, m, u = scores.shape
     nbytes = _cand_bytes(cand, b, m)
-    n_heads = 2 if mode == SELECT_MIOU else 1
+    n_heads = 1 if mode == SELECT_IOU else 2
     if counts is not None:
         counts = counts.to(device=scores.device, dtype=torch.int32).contiguous()
     best_idx, best_score, keep, out = _select_outputs(b, cand)

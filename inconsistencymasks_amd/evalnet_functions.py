@@ -717,10 +717,10 @@ def _copy_last_generation(last_gen_main_path, main_output_path, subs):
         F._dist().barrier()
 
 
-def _run_selection(evalnets, images_path, c, flip, threshold, load, emit):
+def _run_selection(evalnets, images_path, c, flip, threshold, load, emit, mode=None):
     """Shared body of the selection writers: this rank's shard of the file list in batches of SELECT_BATCH images;
     load(pool, chunk) -> (input B of the nets u8 [B,M,...], what is written for a candidate u8 [B,M,...], candidates per image);
-    emit(name, chosen bytes) -> PNG jobs of a kept image."""
+    emit(name, chosen bytes) -> PNG jobs of a kept image.  mode: the rule (evalnet.SELECT_*); None = the ensemble rule of the nets' heads."""
     from .evalnet import SELECT_MAX_CAND, CandidateScorer
     F = _F()
     scorer = CandidateScorer(evalnets)
@@ -740,7 +740,7 @@ def _run_selection(evalnets, images_path, c, flip, threshold, load, emit):
             if nbytes % 16:      # the gather moves 16 bytes at a time
                 cand = torch.nn.functional.pad(cand, (0, 16 - nbytes % 16))
             cnt = None if all(v == m for v in counts) else torch.tensor(counts, dtype=torch.int32, device="cuda")
-            _, _, keep, out = scorer.run(x, xb, cand.contiguous(), threshold, cnt)
+            _, _, keep, out = scorer.run(x, xb, cand.contiguous(), threshold, cnt, mode)
             keep, out = keep.cpu().numpy(), out.cpu().numpy()[:, :nbytes]
             jobs = []
             for i, name in enumerate(chunk):
@@ -844,6 +844,54 @@ def create_training_data_for_segnet_with_miou_ensemble_hela(evalnets, h, w, c, b
         return [(os.path.join(out["alive"], name), alive), (os.path.join(out["dead"], name), dead),
                 (os.path.join(out["mod_position"], name), F._hela_vote_positions(pos, max_pos_circle_size, min_pos_circle_size))]
     _run_selection(evalnets, bf_images_path_in, c, False, threshold, load, emit)
+
+
+# ---------------------------------------------------------------------------------------------------
+# single-EvalNet selection baseline (functions.py:4991-5063, 5583-5677; ISIC_2018/10_ISIC_2018_evalnet.py, SUIM/11_SUIM_evalnet_miou.py):
+# the writers above with one EvalNet.  ISIC: the arg-max of the one net's predicted IoU = SELECT_IOU with N = 1.  Multi-class: a rule of
+# its own (SELECT_CONF_GATED): a class counts if its detection value, averaged over the image's candidates, reaches 0.03, and a
+# candidate's score is the mean of its detection values over the counting classes -- the predicted ious are not used.
+# ---------------------------------------------------------------------------------------------------
+def create_training_data_for_segnet_ISIC_2018(evalnet_model, h, w, c, images_path, mask_paths, main_output_path, threshold,
+                                              last_gen_main_path='', rgb=True):
+    """functions.py:4991-5063: images/ (the file, copied) and masks/ (the candidate with the best predicted IoU) of every unlabeled
+    image whose best predicted IoU reaches `threshold`."""
+    from .evalnet import SELECT_IOU
+    iout, mout = os.path.join(main_output_path, "images"), os.path.join(main_output_path, "masks")
+    os.makedirs(iout, exist_ok=True)
+    os.makedirs(mout, exist_ok=True)
+    _copy_last_generation(last_gen_main_path, main_output_path, ("images", "masks"))
+
+    def emit(name, chosen):
+        shutil.copy(os.path.join(images_path, name), os.path.join(iout, name))
+        return [(os.path.join(mout, name), chosen.reshape(h, w))]
+    _run_selection([evalnet_model], images_path, c, (not rgb) and c == 3, threshold, _mask_candidates(mask_paths, mout, h, w, False), emit,
+                   SELECT_IOU)
+
+
+def create_training_data_by_evalnet_miou_for_segnet_multiclass(evalnet_model, h, w, c, num_classes, images_path, mask_paths,
+                                                               main_output_path, miou_threshold, last_gen_main_path='', rgb=True):
+    """functions.py:5583-5677: as the writer above with class-id masks; a class counts for an image if the mean of its detection
+    value over the image's candidates is at least 0.03, the score of a candidate is the mean of its detection values over the counting
+    classes (0 if there is none), and the best candidate is kept if its score reaches `miou_threshold`."""
+    from .evalnet import SELECT_CONF_GATED
+    iout, mout = os.path.join(main_output_path, "images"), os.path.join(main_output_path, "masks")
+    os.makedirs(iout, exist_ok=True)
+    os.makedirs(mout, exist_ok=True)
+    _copy_last_generation(last_gen_main_path, main_output_path, ("images", "masks"))
+    class_ids = _takes_class_ids([evalnet_model])
+
+    def emit(name, chosen):
+        shutil.copy(os.path.join(images_path, name), os.path.join(iout, name))
+        return [(os.path.join(mout, name), chosen.reshape(h, w))]
+    load = _mask_candidates(mask_paths, mout, h, w, class_ids)
+    if not class_ids:      # models that take the one-hot stack (functions.py:5642)
+        ids = load
+
+        def load(pool, chunk):
+            xb, cand, counts = ids(pool, chunk)
+            return (xb == torch.arange(num_classes, device=xb.device, dtype=xb.dtype)).to(torch.uint8), cand, counts
+    _run_selection([evalnet_model], images_path, c, (not rgb) and c == 3, miou_threshold, load, emit, SELECT_CONF_GATED)
 
 
 # ---------------------------------------------------------------------------------------------------

@@ -1872,6 +1872,8 @@ from .evalnet_functions import (compute_classwise_detection, compute_classwise_d
                                 create_training_data_evalnet_im_binary, create_training_data_evalnet_ISIC_2018,
                                 create_training_data_evalnet_miou_hela, create_training_data_evalnet_miou_im_hela,
                                 create_training_data_evalnet_miou_im_multiclass, create_training_data_evalnet_miou_multiclass,
+                                create_training_data_by_evalnet_miou_for_segnet_multiclass,
+                                create_training_data_for_segnet_ISIC_2018,
                                 create_training_data_for_segnet_with_ensemble_binary,
                                 create_training_data_for_segnet_with_miou_ensemble_hela,
                                 create_training_data_for_segnet_with_miou_ensemble_multiclass, load_evalnet, num_augs_from_miou,

@@ -7,7 +7,16 @@ generations 0..4: every unlabeled image's candidate masks (generation 0: the pre
 previous generation's 5 candidates, plus the pair selected last generation) are scored by the n best EvalNets, the best candidate is
 kept where its score reaches the threshold (create_training_data_for_segnet_with_*ensemble*: one fused call per batch), the labelled
 pairs join the selected set, and 5 U-Net candidates are trained on it and ranked.  Same loops, model / directory / CSV names.
-Environment overrides for short runs: IM_RUNIDS, IM_NS, IM_GENS, IM_CANDIDATES, IM_EVALNET_CANDIDATES (comma-separated)."""
+Environment overrides for short runs: IM_RUNIDS, IM_NS, IM_GENS, IM_CANDIDATES, IM_EVALNET_CANDIDATES (comma-separated).
+
+run(dataset, ensemble=False) is the single-EvalNet baseline the ensemble row is measured against: ISIC_2018/10_ISIC_2018_evalnet.py and
+SUIM/11_SUIM_evalnet_miou.py (copies of one template; HeLa and Cityscapes have no such script).  EvalNet training data under
+`evalnet/run_{runid}`: EVERY `subset` and `subset_aug` model writes train and val, the `subset_aug` models from TRAIN_LABELED_AUG.  One
+EvalNet per run id (`{TAG}_evalnet_{runid}.h5` / `SUIM_evalnet_miou_{runid}.h5`), no candidates, no ranking; its results CSV has the
+header modelname;mse;mae in both scripts -- SUIM's over a row of its five values without a name.  Generations 0..4 without the n loop,
+the threshold from [ISIC_2018] MAX_THRESHOLD / [DEFAULT] THRESHOLD, the candidates chosen by
+create_training_data_for_segnet_ISIC_2018 / create_training_data_by_evalnet_miou_for_segnet_multiclass, STEPS_PER_EPOCH = images //
+BATCH_SIZE without the third-of-the-full-set floor.  Overrides: IM_RUNIDS, IM_GENS, IM_CANDIDATES."""
 import csv
 import os
 import shutil
@@ -45,7 +54,23 @@ def csv_header(dataset):
     return NOISY_STUDENT_HELA_HEADER if DATASETS[dataset]["kind"] == "hela" else DATASETS[dataset]["header"]
 
 
-def run(dataset, train_new_evalnet=True):
+SINGLE_DATASETS = ("ISIC_2018", "SUIM")      # the datasets that have a single-EvalNet script
+SINGLE_HEADER = ["modelname", "mse", "mae"]      # both scripts; SUIM's row below it has five values and no name (:98-99)
+SINGLE_THRESHOLD_KEY = {"ISIC_2018": ("ISIC_2018", "MAX_THRESHOLD"), "SUIM": ("DEFAULT", "THRESHOLD")}      # line 34 / 40
+
+
+def single_names(dataset):
+    """(tag, EvalNet name stem, EvalNet data directory, U-Net name stem) of a dataset's single-EvalNet script"""
+    if dataset not in SINGLE_DATASETS:
+        raise ValueError(f"the reference has no single-EvalNet script for {dataset}: only {', '.join(SINGLE_DATASETS)}")
+    if DATASETS[dataset]["kind"] == "isic":
+        return dataset, f"{dataset}_evalnet", "evalnet", f"{dataset}_segnet"
+    return dataset, f"{dataset}_evalnet_miou", "evalnet", f"{dataset}_segnet_miou"
+
+
+def run(dataset, train_new_evalnet=True, ensemble=True):
+    if not ensemble:
+        return _run_single(dataset, train_new_evalnet)
     kind = DATASETS[dataset]["kind"]            # isic | hela | multi
     hela, multi = kind == "hela", kind == "multi"
     tag, evalnet_tag, ev_sub, segnet_tag = names(dataset)
@@ -186,3 +211,119 @@ def run(dataset, train_new_evalnet=True):
                         wr.writerow(csv_header(dataset))
                         wr.writerows(rows)
                 barrier()
+
+
+def _run_single(dataset, train_new_evalnet=True):
+    """the single-EvalNet loop (module docstring)"""
+    tag, evalnet_tag, ev_sub, segnet_tag = single_names(dataset)
+    multi = DATASETS[dataset]["kind"] == "multi"
+    S, D = F.config[tag], F.config["DEFAULT"]
+    H, W, C, K = int(S["IMAGE_HEIGHT"]), int(S["IMAGE_WIDTH"]), int(S["IMAGE_CHANNELS"]), int(S["NUM_CLASSES"])
+    alpha, alpha_evalnet = float(S["ALPHA"]), float(S["ALPHA_EVALNET"])
+    actifu, actifu_out = S["ACTIFU"], S["ACTIFU_OUTPUT"]
+    section, key = SINGLE_THRESHOLD_KEY[dataset]
+    threshold = float(F.config[section][key])
+    batch, top_k = int(D["BATCH_SIZE"]), int(D["TOP_Ks"])
+    bs_evalnet, ep_evalnet = int(D["BATCH_SIZE_EVALNET"]), int(D["NUM_EPOCHS_EVALNET"])
+    P = lambda name: getattr(paths, f"{tag}_{name}")
+    base, model_dir, csv_dir = P("BASE_DIR"), P("MODEL_DIR"), P("CSV_DIR")
+    F.init_distributed()
+    rank, world = F._rank_world()
+    barrier = lambda: torch.distributed.barrier() if torch.distributed.is_initialized() else None
+    os.makedirs(csv_dir, exist_ok=True)
+
+    def evalnet_data(model, split, out_dir, model_i):
+        if multi:
+            F.create_training_data_evalnet_miou_multiclass(model, H, W, C, K, P(f"{split}_IMAGES_DIR"), P(f"{split}_MASKS_DIR"), out_dir,
+                                                           model_i)
+        else:
+            F.create_training_data_evalnet_ISIC_2018(model, H, W, C, P(f"{split}_IMAGES_DIR"), P(f"{split}_MASKS_DIR"), out_dir, model_i)
+
+    for runid in _ints("IM_RUNIDS", RUNIDS):
+        evalnet_name = f"{evalnet_tag}_{runid}"
+        evalnet_h5 = os.path.join(model_dir, evalnet_name + ".h5")
+        if train_new_evalnet:
+            ev_dir = os.path.join(base, ev_sub, f"run_{runid}")
+            tr, va = os.path.join(ev_dir, "train"), os.path.join(ev_dir, "val")
+            for (first, which), split in zip(EVALNET_SOURCES, ("TRAIN_LABELED", "TRAIN_LABELED_AUG")):      # :55-85
+                model_i = first
+                for fname in sorted(os.listdir(model_dir)):
+                    if f"{tag}_{which}_{runid}" in fname:
+                        model = F.load_model(os.path.join(model_dir, fname))
+                        evalnet_data(model, split, tr, model_i)
+                        evalnet_data(model, "VAL", va, model_i)      # every model: no first-three limit here
+                        model_i += 1
+                        del model
+            if multi:
+                evalnet = get_evalnet_miou(H, W, C, K, alpha_evalnet, seed=9000 * runid, onehot_B=True)
+                res = F.train_evalnet_miou_model_multiclass(evalnet, H, W, tr, va, evalnet_h5, bs_evalnet, K, ep_evalnet)
+                row = list(res)      # total_loss, iou_loss, conf_loss, iou_mae, conf_mae under the three-name header, as the script writes it
+            else:
+                evalnet = get_evalnet(H, W, C, K, alpha_evalnet, normalize_B=True, seed=9000 * runid)
+                res = F.train_evalnet_ISIC_2018(evalnet, tr, va, evalnet_h5, bs_evalnet, ep_evalnet)
+                row = [evalnet_name, *res]
+            del evalnet
+            if rank == 0:
+                with open(os.path.join(csv_dir, f"results_{evalnet_name}.csv"), "w", encoding="utf-8", newline="") as f:
+                    wr = csv.writer(f, delimiter=";")
+                    wr.writerow(SINGLE_HEADER)
+                    wr.writerow(row)
+            barrier()
+
+        for gen in _ints("IM_GENS", GENS):
+            name_of = lambda g: f"{segnet_tag}_{runid}_gen{g}"
+            modelname = name_of(gen)
+            pred_dir = lambda k, name: os.path.join(base, f"{k}_predictions", "segnet", name)
+            unl = pred_dir("train_unlabeled", modelname)
+            evalnet = F.load_evalnet(evalnet_h5)
+            if gen == 0:
+                mask_dirs = [os.path.join(base, "train_unlabeled_predictions", "subset", f"{tag}_subset_{runid}_{j}")
+                             for j in range(N_SUBSET_MODELS)]
+                last = ()
+            else:      # the previous generation's candidates (0..4 in the scripts) and its selected set
+                mask_dirs = [pred_dir("train_unlabeled", f"{name_of(gen - 1)}_{j}") for j in _ints("IM_CANDIDATES", CANDIDATES)]
+                last = (pred_dir("train_unlabeled", name_of(gen - 1)),)
+            if multi:
+                F.create_training_data_by_evalnet_miou_for_segnet_multiclass(evalnet, H, W, C, K, P("TRAIN_UNLABELED_IMAGES_DIR"), mask_dirs,
+                                                                             unl, threshold, *last)
+            else:
+                F.create_training_data_for_segnet_ISIC_2018(evalnet, H, W, C, P("TRAIN_UNLABELED_IMAGES_DIR"), mask_dirs, unl, threshold, *last)
+            del evalnet
+            if rank == 0:      # the labelled pairs join the selected set
+                lab = P("TRAIN_LABELED_DIR")
+                for name in os.listdir(os.path.join(lab, "images")):
+                    for sub in ("images", "masks"):
+                        shutil.copy(os.path.join(lab, sub, name), os.path.join(unl, sub, name))
+            barrier()
+            train_dir = os.path.join(unl, "images")
+            steps = epoch_steps(len(os.listdir(train_dir)), batch, world)      # no floor from the full set in these two scripts
+
+            def train_candidate(i, side_by_side=False):
+                name_i = f"{modelname}_{i}"
+                h5 = os.path.join(model_dir, name_i + ".h5")
+                preds = [pred_dir(k, name_i) for k in ("val", "test", "train_unlabeled")]
+                model = get_unet(H, W, C, K, alpha, actifu, actifu_out, seed=1000 * runid + 100 * gen + i)
+                if side_by_side:      # the other candidates' streams fill this one's gaps: no side stream of its own (results identical)
+                    model.debug(single_stream=True)
+                if multi:
+                    res = F.train_multiclass(train_dir, P("VAL_IMAGES_DIR"), P("VAL_MASKS_DIR"), P("TEST_IMAGES_DIR"),
+                                             P("TEST_MASKS_DIR"), P("TRAIN_UNLABELED_IMAGES_DIR"), P("TRAIN_UNLABELED_MASKS_DIR"),
+                                             name_i, h5, model, "categorical_crossentropy", steps, H, W, C, K,
+                                             color_mapping(dataset, K), *preds)
+                else:
+                    res = F.train_ISIC_2018(train_dir, P("VAL_IMAGES_DIR"), P("VAL_MASKS_DIR"), P("TEST_IMAGES_DIR"),
+                                            P("TEST_MASKS_DIR"), P("TRAIN_UNLABELED_IMAGES_DIR"), P("TRAIN_UNLABELED_MASKS_DIR"),
+                                            name_i, h5, model, "mse", steps, H, W, C, *preds)
+                del model
+                return (name_i,) + tuple(res)
+            rows = train_candidates(_ints("IM_CANDIDATES", CANDIDATES), train_candidate, world)
+            if rank == 0:
+                top = sorted(rows, key=lambda r: r[DATASETS[dataset]["rank"]], reverse=True)[:top_k]
+                print(top)
+                for i, row in enumerate(top, start=1):
+                    os.rename(os.path.join(model_dir, f"{row[0]}.h5"), os.path.join(model_dir, f"{row[0][:-2]}_topK_{i}.h5"))
+                with open(os.path.join(csv_dir, f"results_{modelname}.csv"), "w", encoding="utf-8", newline="") as f:
+                    wr = csv.writer(f, delimiter=";")
+                    wr.writerow(DATASETS[dataset]["header"])
+                    wr.writerows(rows)
+            barrier()

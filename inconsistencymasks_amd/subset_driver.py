@@ -8,7 +8,11 @@ Environment overrides for short runs: IM_RUNIDS, IM_CANDIDATES (comma-separated)
 run(dataset, aug=True) is the augmented-subset baseline (ALDT: ISIC_2018/04_ISIC_2018_subset_aug.py:34-43, HeLa/04_HeLa_subset_aug.py,
 Cityscapes/04_Cityscapes_subset_aug.py, SUIM/05_SUIM_subset_aug.py): the labelled set is first augmented into
 TRAIN_LABELED_AUG with the functions' default arguments, the candidates train on that, names carry `subset_aug` -- the
-generation-0 ensemble of the AIM+ drivers (im_driver.run(..., approach="aug_IM_plus"))."""
+generation-0 ensemble of the AIM+ drivers (im_driver.run(..., approach="aug_IM_plus")).
+
+run(dataset, full=True) is the full-dataset baseline, the upper bound of the paper's tables (ISIC_2018/02_ISIC_2018_full_dataset.py,
+HeLa/02_HeLa_full_dataset.py, Cityscapes/02_Cityscapes_full_dataset.py, SUIM/03_SUIM_full_dataset.py): the same loop on TRAIN_FULL,
+names carry `full_dataset`; ranking keys, headers and renames are the subset baseline's."""
 import csv
 import os
 
@@ -16,12 +20,18 @@ import torch
 
 from . import functions as F
 from . import paths
-from .im_driver import DATASETS, _ints, color_mapping, epoch_steps, train_candidates
+from .im_driver import DATASETS, NOISY_STUDENT_HELA_HEADER, _ints, color_mapping, epoch_steps, train_candidates
 from .unet import get_unet
 
 # (index of the ranking value in the row, descending?) -- ISIC_2018/03_ISIC_2018_subset.py:82, SUIM/04_SUIM_subset.py:84,
 # HeLa/03_HeLa_subset.py:82 (`key=lambda x: x[6], reverse=False`)
 _RANK = {"isic": (1, True), "multi": (4, True), "hela": (6, False)}
+
+
+def csv_header(dataset, full=False):
+    """HeLa/02_HeLa_full_dataset.py:96 abbreviates the cell-count columns (`mcce_*`), as the noisy-student script does"""
+    ds = DATASETS[dataset]
+    return NOISY_STUDENT_HELA_HEADER if full and ds["kind"] == "hela" else ds["header"]
 
 
 def train_candidate(ds, dataset, train_dir, name_i, h5, model, steps, H, W, C, K, preds):
@@ -40,7 +50,9 @@ def train_candidate(ds, dataset, train_dir, name_i, h5, model, steps, H, W, C, K
                         P("TRAIN_UNLABELED_DIR"), name_i, h5, model, "mse", steps, H, W, C, *preds)
 
 
-def run(dataset, aug=False):
+def run(dataset, aug=False, full=False):
+    if aug and full:
+        raise ValueError("aug and full are different baselines")
     ds = DATASETS[dataset]
     S = F.config[ds["section"]]
     H, W, C = int(S["IMAGE_HEIGHT"]), int(S["IMAGE_WIDTH"]), int(S["IMAGE_CHANNELS"])
@@ -51,7 +63,7 @@ def run(dataset, aug=False):
     F.init_distributed()
     rank, world = F._rank_world()
     tag = {"HeLa": "HELA", "Cityscapes": "CITYSCAPES"}.get(dataset, dataset)
-    approach = "subset_aug" if aug else "subset"
+    approach = "full_dataset" if full else "subset_aug" if aug else "subset"
     if aug:     # default arguments, as the reference's scripts call them
         if ds["kind"] == "isic":
             F.create_augment_images_and_masks_ISIC_2018(P("TRAIN_LABELED_IMAGES_DIR"), P("TRAIN_LABELED_MASKS_DIR"), P("TRAIN_LABELED_AUG_MAIN_DIR"))
@@ -61,7 +73,7 @@ def run(dataset, aug=False):
             F.create_augment_images_and_masks_hela(P("TRAIN_LABELED_DIR"), P("TRAIN_LABELED_AUG_DIR"))
         if torch.distributed.is_initialized():
             torch.distributed.barrier()
-    lab = "TRAIN_LABELED_AUG" if aug else "TRAIN_LABELED"
+    lab = "TRAIN_FULL" if full else "TRAIN_LABELED_AUG" if aug else "TRAIN_LABELED"
     train_dir = os.path.join(P(f"{lab}_DIR"), "brightfield") if ds["kind"] == "hela" else P(f"{lab}_IMAGES_DIR")
     steps = epoch_steps(len(os.listdir(train_dir)), batch, world)
     os.makedirs(model_dir, exist_ok=True)
@@ -88,7 +100,7 @@ def run(dataset, aug=False):
             os.makedirs(csv_dir, exist_ok=True)
             with open(os.path.join(csv_dir, f"results_{modelname}.csv"), "w", encoding="utf-8", newline="") as f:
                 wr = csv.writer(f, delimiter=";")
-                wr.writerow(ds["header"])
+                wr.writerow(csv_header(dataset, full))
                 wr.writerows(rows)
         if torch.distributed.is_initialized():
             torch.distributed.barrier()
