@@ -30,6 +30,11 @@
  *   - every byte of an output is written, except where an output is stated to be unused on a route: such a buffer is not touched
  *     and may be NULL;
  *   - a workspace smaller than the call needs is refused with IMK_EWORKSPACE before anything is launched or written.
+ *
+ * Streams (all entry points; tests/test_gpu_stream_order.py holds the six that fork to this with skewed streams and poison fills):
+ *   - every call leaves all of its work, including work on the pool's side streams, ordered after prior work on `stream` and
+ *     before later work on `stream`: what the caller enqueued on `stream` before the call is visible to every kernel of the call, and
+ *     what it enqueues on `stream` behind the call (reading an output, overwriting an input or the workspace) sees the call finished.
  */
 #ifndef IMK_H
 #define IMK_H
