@@ -556,6 +556,48 @@ IMK_API int imk_mod_pos_size(const uint8_t *img, int h, int w, int max_r, int mi
 IMK_API int imk_cell_count(const int32_t *xy, int n, const uint8_t *alive, const uint8_t *dead, int h, int w,
                            int measuring_range, int32_t counts[3]);
 
+/* ------------------------------------------------------------------------------------------------
+ * Data preparation (csrc/imk_prep.hip): the pixel rules of the reference's 00_* / 01_* / SUIM 02_* scripts, which go through
+ * cv2.resize, cv2.cvtColor and cv2.threshold.  The rules are restated from OpenCV 4's published sources (imgproc/src/resize.cpp,
+ * imgproc/src/color_rgb.simd.hpp as of 4.x: 8-bit grey with 15-bit coefficients); they are not pinned against OpenCV itself.
+ * DEVICE pointers unless stated; not in place.
+ *
+ * imk_prep_resize: a ragged batch in one launch.  src holds n decoded sources [src_h, src_w, c] u8 back to back (src_bytes in
+ * all); item i resizes the rectangle (x0, y0, cw, ch) of the source at src + src_off to out[i] [dh, dw, c].  scale_x / scale_y
+ * are 1.0 / ((double)dw / cw) and 1.0 / ((double)dh / ch), formed by the host as cv::resize forms 1 / inv_scale.  An item whose
+ * rectangle leaves its source, or whose source leaves [0, src_bytes), is written as zeros (nothing is read for it).
+ *   IMK_PREP_LINEAR   cv2.resize's default for 8-bit data: per axis f = (float)((d + 0.5) * scale - 0.5) (product and sum rounded
+ *                     separately in double), s = floor(f), f -= s; on x, s < 0 -> (0, 0) and s >= cw - 1 -> (cw - 1, 0); on y the
+ *                     rows s, s + 1 are clamped into the rectangle; weights rint(. * 2048) (half to even, saturated to int16);
+ *                     H = S[s] a0 + S[s + 1] a1; out = (((b0 (H0 >> 4)) >> 16) + ((b1 (H1 >> 4)) >> 16) + 2) >> 2.
+ *                     cw == 2 dw and ch == 2 dh: (p00 + p01 + p10 + p11 + 2) >> 2, as cv::resize switches to its area rule.
+ *   IMK_PREP_NEAREST  sx = min((int)floor(dx * scale_x), cw - 1) in double, the same on y.
+ *   post = IMK_PREP_LABEL_PLUS1: v > 0 ? (uint8)(v + 1) : v  (np.where(m > 0, m + 1, m) on uint8: 255 wraps to 0).
+ * c is 1 or 3 (else IMK_EUNSUPPORTED); n <= 65535; dh * dw * c < 2^31.
+ * ---------------------------------------------------------------------------------------------- */
+enum { IMK_PREP_LINEAR = 0, IMK_PREP_NEAREST = 1 };
+enum { IMK_PREP_LABEL_PLUS1 = 1 };
+typedef struct imk_prep_item {    /* one per output image, device array [n] */
+    int64_t src_off;              /* byte offset of the decoded source inside src */
+    int src_h, src_w;
+    int x0, y0, cw, ch;           /* the crop rectangle inside the source; the whole image is (0, 0, src_w, src_h) */
+    double scale_x, scale_y;
+} imk_prep_item;
+IMK_API int imk_prep_resize(const uint8_t *src, int64_t src_bytes, const imk_prep_item *items, int n, int c, int dh, int dw,
+                            int interp, int post, uint8_t *out, void *stream);
+
+/* imk_prep_crops: one source [h, w, c] u8 (c = 1 or 3) -> P planes out [P, ch, cw] u8; pos device int32 [P, 2] of (x, y), the
+ * crop's top-left corner.  The whole image is the one crop at (0, 0) with cw = w, ch = h.  A crop pixel outside the source is
+ * written as 0 (nothing is read for it).  b_first != 0: byte 0 of a pixel is B (cv2.imread's order), else R.
+ *   IMK_PREP_GRAY         c == 3: (R 9798 + G 19235 + B 3735 + 16384) >> 15 (cv2.cvtColor(BGR2GRAY), 8 bit); c == 1: a copy
+ *   IMK_PREP_GRAY_THRESH  the grey value > 10 ? 255 : 0                                  (cv2.threshold(., 10, 255, THRESH_BINARY))
+ *   IMK_PREP_CLASS8       c == 3 only: class_table[(R >= 128) << 2 | (G >= 128) << 1 | (B >= 128)]; class_table is a HOST
+ *                         pointer to 8 bytes, read during the call (NULL for the other rules)
+ * ---------------------------------------------------------------------------------------------- */
+enum { IMK_PREP_GRAY = 0, IMK_PREP_GRAY_THRESH = 1, IMK_PREP_CLASS8 = 2 };
+IMK_API int imk_prep_crops(const uint8_t *src, int h, int w, int c, const int32_t *pos, int n_crops, int ch, int cw, int rule,
+                           const uint8_t *class_table, int b_first, uint8_t *out, void *stream);
+
 /* Runtime environment checks.  imk_runtime_warnings() returns a bit mask of conditions the library has noticed so far in this
  * process (it also prints each once to stderr):
  *   IMK_WARN_HW_QUEUES  a side stream was requested (training step, ensemble forward) while GPU_MAX_HW_QUEUES is unset or

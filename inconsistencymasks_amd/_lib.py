@@ -29,6 +29,11 @@ class ViewParams(ctypes.Structure):
                 ("alpha", c_float), ("beta", c_float)]
 
 
+class PrepItem(ctypes.Structure):
+    _fields_ = [("src_off", c_int64), ("src_h", c_int), ("src_w", c_int), ("x0", c_int), ("y0", c_int), ("cw", c_int),
+                ("ch", c_int), ("scale_x", ctypes.c_double), ("scale_y", ctypes.c_double)]
+
+
 class LayerInfo(ctypes.Structure):
     _fields_ = [("name", ctypes.c_char * 16), ("kind", c_int), ("ksize", c_int), ("cin", c_int), ("cout", c_int),
                 ("off_w", c_int64), ("off_b", c_int64), ("off_mean", c_int64), ("off_var", c_int64)]
@@ -130,6 +135,9 @@ SIGNATURES = {
     "imk_pos_contours": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int]),
     "imk_mod_pos_size": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "imk_cell_count": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "imk_prep_resize": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "imk_prep_crops": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
+                               c_void_p]),
     "imk_unet_adamw_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float,
                                     c_float, c_float, c_float, c_float, c_float, c_void_p]),
 }
