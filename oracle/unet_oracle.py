@@ -172,6 +172,15 @@ def _bn(x, p, name, training, f16, stats_out):
     return x * scale[None, :, None, None] + shift[None, :, None, None]
 
 
+def head(y, w, b, act_out):
+    """The output layer (unet.py:63) on the NCHW input y, in the dtype of its arguments: Conv1x1 with the HWIO kernel w [1,1,ci,K] and
+    bias b, then sigmoid or softmax over the classes -> (probabilities, logits), NCHW.  forward() calls it in float32;
+    oracle/head_oracle.py is checked against it in float64 (tests/test_cpu_head_oracle.py)."""
+    logits = F.conv2d(y, w.permute(3, 2, 0, 1), b)
+    probs = torch.sigmoid(logits) if act_out == "sigmoid" else torch.softmax(logits, dim=1)
+    return probs, logits
+
+
 def forward(p, x_u8_nhwc, c_in, n_out, alpha, act_out, training=False, emulate_fp16=False,
             stats_out=None, taps=None, override=None, return_logits=False, grad_taps=None):
     """x uint8 [B,H,W,C] (numpy or torch) -> probabilities float32 [B,H,W,K] (torch).
@@ -220,9 +229,7 @@ def forward(p, x_u8_nhwc, c_in, n_out, alpha, act_out, training=False, emulate_f
         a = bn(f"d{j}.bna", c(f"d{j}.ca", u))
         y = bn(f"d{j}.bnb", c(f"d{j}.c1", c(f"d{j}.c3", a)))
     # head: fp32 weights, fp32 math on the (fp16-valued) input  (unet.py:63 dtype='float32')
-    w = p["out.w"].permute(3, 2, 0, 1)
-    logits = F.conv2d(y, w, p["out.b"])
-    probs = torch.sigmoid(logits) if act_out == "sigmoid" else torch.softmax(logits, dim=1)
+    probs, logits = head(y, p["out.w"], p["out.b"], act_out)
     probs = probs.permute(0, 2, 3, 1).contiguous()
     if return_logits:
         return probs, logits.permute(0, 2, 3, 1).contiguous()
