@@ -236,6 +236,14 @@ IMK_API int imk_unet_forward_vote(const imk_unet_plan *plan, int n_models,
  * backward, optimizer.  Split in two so that a data-parallel caller can all-reduce `grads` in between.
  *   loss_kind 0 = 'mse' on {0,1} targets y u8 [B,H,W,n_out]   (ISIC, HeLa)
  *             1 = categorical cross-entropy, y u8 [B,H,W] class ids (one-hot formed on the fly)
+ *             2 = 'mse' on the continuous targets float32(y) / 255.0f (a correctly rounded divide), y u8 [B,H,W,n_out] as
+ *                 parse_image_depth_map builds it (functions.py:1051-1073); sigmoid heads.  With y in {0,255} it is kind 0 with
+ *                 y in {0,1}, bit for bit.
+ *             3 = the reference's rmse (functions.py:36-37), sqrt(mean (p - y)^2) on the targets of kind 2: kind 2, then one launch
+ *                 over the gradient vector behind the loss finalize, on `stream`: grads[i] *= 0.5f / sqrtf(mse), stats[0] =
+ *                 sqrtf(mse).  A batch with mse == 0 sets the overflow flag stats[1] and is skipped by imk_unet_adamw_step (Keras'
+ *                 loss-scale optimizer skips the NaN gradient TensorFlow produces there).  A rank's rmse is not the batch's: do
+ *                 not average kind-3 gradients over data-parallel ranks.
  *   grads     [trainable] float32, UNSCALED gradient of the mean loss
  *   stats     device float[4]: {loss, found_inf (0/1), loss_scale used, reserved}
  *   state     device buffer of imk_unet_state_bytes(): Adam m, v, step counter, dynamic loss scale
@@ -410,6 +418,54 @@ IMK_API int imk_eval_multiclass(const float *probs, const uint8_t *gt, int batch
  * out: device buffer of imk_eval_soft_out_doubles(K) doubles (results first, block partials behind them); K <= 64. */
 IMK_API int64_t imk_eval_soft_out_doubles(int k);
 IMK_API int imk_eval_soft_sums(const float *probs, const uint8_t *gt, int64_t n_pix, int k, int mode, double *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Depth-map (regression) family (csrc/imk_depth.hip): get_im_prediction_depth_map (functions.py:6155-6177), benchmark_depth_map
+ * (:1345-1384), rmse / delta_metric (:36-48)
+ * ---------------------------------------------------------------------------------------------- */
+/* The standard-deviation IM: a pixel is inconsistent where the ensemble's per-pixel standard deviation exceeds mult times the
+ * image's mean standard deviation.  Every image of the batch gets its own threshold (the reference works on one prepared image; one
+ * threshold over a whole batch, as it forms when handed one, is this call with batch 1 and height B*H: the element order is the same).
+ *   preds    [N,B,H,W] float32 (one output map), 2 <= N <= 16, else IMK_EUNSUPPORTED; H*W <= 2^24 and B <= 65535, else IMK_EUNSUPPORTED
+ *   img      [B,H,W,C] uint8 or NULL;  img_out = img with IM pixels zeroed if block_in (ignored when img == NULL)
+ *   im_out   [B,H,W] uint8 {0,255};  im_size [B] int64;  thr_out [B] float32, the thresholds
+ *   std_out  [B,H,W] float32 or NULL: the standard-deviation map.  Given, it serves as the call's map and the workspace is not touched
+ *            (it may be NULL then); otherwise the map lives in the workspace, imk_im_depth_workspace_bytes(B, H, W) bytes.
+ * Bit-exact against numpy's float32 np.std(axis=-1) -> mult * np.mean -> `>` given identical predictions: float32 throughout, every
+ * operation rounded on its own (no fused multiply-add; correctly rounded divides and square roots), sums in numpy's order -- over the
+ * models eight strided accumulators from N = 8 on, over the image the pairwise recursion down to leaves of at most 128 elements inside
+ * chunks of 8192 elements that are added sequentially (csrc/imk_depth.hip states the order in full).  mult is the float32 multiplier:
+ * numpy >= 2 forms float32(mult) * mean in float32; numpy < 2 forms the product in double and rounds once, the same value for every
+ * multiplier representable in float32.  NaN propagates: one NaN prediction makes the image's threshold NaN and its whole IM zero. */
+IMK_API int64_t imk_im_depth_workspace_bytes(int batch, int h, int w);
+IMK_API int imk_im_depth(const float *preds, int n_models, int batch, int h, int w, float mult, const uint8_t *img, int c,
+                         int block_in, uint8_t *img_out, uint8_t *im_out, int64_t *im_size, float *thr_out, float *std_out,
+                         void *workspace, int64_t workspace_bytes, void *stream);
+
+/* Ensemble inference fused with the standard-deviation IM, in the shape of imk_unet_forward_im: N models' forward passes (sigmoid
+ * heads with one map; `params` / `packed` host arrays of N device pointers; the models on k <= min(N, 3) streams forked from and
+ * joined to `stream`), then imk_im_depth's rule on their probabilities; outputs as imk_im_depth (std_out may be NULL; img = the
+ * plan's c_in channels).  The first launch of the rule reads the N last decoder activations (fp16) and forms every model's probability
+ * with the code of imk_unet_forward's head, so the fp32 probability stack is never written and the outputs are bit-identical to
+ * imk_unet_forward x N + imk_im_depth.  The fused launch covers last decoder widths 8 / 16 / 24 / 32 and N <= 8; other shapes (N up
+ * to 16) and plans with the materialize debug switch take the unfused route through the stack inside the same call.
+ * workspace: imk_unet_forward_im_depth_workspace_bytes(plan, N, B, k) = imk_unet_forward_im_workspace_bytes + the std map. */
+IMK_API int64_t imk_unet_forward_im_depth_workspace_bytes(const imk_unet_plan *plan, int n_models, int batch, int n_streams);
+IMK_API int imk_unet_forward_im_depth(const imk_unet_plan *plan, int n_models, const float *const *params,
+                                      const void *const *packed, const uint8_t *x, int batch, float mult, const uint8_t *img,
+                                      int block_in, uint8_t *img_out, uint8_t *im_out, int64_t *im_size, float *thr_out,
+                                      float *std_out, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* Evaluation of a depth-map model: probs [B,H,W] f32, gt [B,H,W] u8 ->
+ *   pred_out [B,H,W] u8 (may be NULL): clip(p * 255.0f, 0, 255) truncated toward zero, NaN -> 0 (benchmark_depth_map's PNG rule)
+ *   sums     [B,2] double, per image and in a summation order fixed by H*W:
+ *            [0] sum (p - y)^2 with y = float32(gt) / 255.0f (a correctly rounded divide), the difference formed in float32 and
+ *                squared and added in double;
+ *            [1] the number of pixels with max(p / y, y / p) < 1.25f in float32; y = 0 and NaN count as false, as tf.maximum and `<`
+ *                leave them.
+ * Per image, so that the host can form Keras' per-batch, batch-size-weighted means (rmse: the mean of per-batch square roots). */
+IMK_API int imk_eval_depth(const float *probs, const uint8_t *gt, int batch, int h, int w, uint8_t *pred_out, double *sums,
+                           void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * EvalNet (evalnet.py:24-73): the quality-scoring network of IM++ / AIM++

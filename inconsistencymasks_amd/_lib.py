@@ -112,6 +112,13 @@ SIGNATURES = {
     "imk_eval_multiclass": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "imk_eval_soft_out_doubles": (c_int64, [c_int]),
     "imk_eval_soft_sums": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p]),
+    "imk_im_depth_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "imk_im_depth": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                             c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "imk_unet_forward_im_depth_workspace_bytes": (c_int64, [c_void_p, c_int, c_int, c_int]),
+    "imk_unet_forward_im_depth": (c_int, [c_void_p, c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_void_p, c_int, c_float,
+                                          c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "imk_eval_depth": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "imk_unet_plan_debug": (c_int, [c_void_p, c_int, c_int]),
     "imk_unet_plan_set_bn_momentum": (c_int, [c_void_p, c_float]),
     "imk_unet_plan_get_bn_momentum": (c_int, [c_void_p, ctypes.POINTER(c_float)]),

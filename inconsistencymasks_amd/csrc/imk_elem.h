@@ -28,7 +28,7 @@ int imk_loss_blocks(long long n_pix);
 // training: head (BN on load, fp32 1x1 conv, sigmoid / softmax) + loss + d(loss * scale)/d(logits), no probability tensor
 int imk_launch_head_loss(const f16 *z, const float *sc, const float *sh, const float *w, const float *bias, int cin, int cs,
                          int K, int softmax, long long n_pix, const uint8_t *y, const ImkCtl *ctl, float *stats,
-                         f16 *dlogit, float *loss_partial, hipStream_t stream);
+                         f16 *dlogit, float *loss_partial, hipStream_t stream, int y255 = 0);   // y255: targets y / 255.0f (sigmoid heads)
 // softmax heads, training: head + loss + gradient of the last BatchNorm's output (+ its statistics) + the output layer's
 // weight / bias gradient partials in ONE pass (imk_headf.hip); rows = workgroups = rows of every partial buffer it writes
 bool imk_head_cce_fused_ok(int cs, int K, long long n_pix, int rows_cap);
@@ -40,7 +40,11 @@ int imk_launch_head_cce_fused(const f16 *z, const float *sc, const float *sh, co
 bool imk_head_mse_fused_ok(int cs, int K, long long n_pix, int rows_cap);
 int imk_launch_head_mse_fused(const f16 *z, const float *sc, const float *sh, const float *w, const float *bias, int cin, int cs,
                               int K, long long n_pix, const uint8_t *y, const ImkCtl *ctl, float *stats, f16 *dy,
-                              float *loss_partial, float *dystat_partial, float *wg_partial, hipStream_t stream);
+                              float *loss_partial, float *dystat_partial, float *wg_partial, hipStream_t stream, int y255 = 0);
+// loss kind 3 (the reference's rmse = sqrt(mse)), behind the mse step's loss finalize: every gradient is linear in the head's logit
+// gradient, so grads[i] *= 0.5f / sqrtf(mse) and stats[0] = sqrtf(mse); mse == 0 sets the overflow flag stats[1] (the step is skipped)
+int imk_launch_rmse_scale(const float *loss_partial, long long n_pix, int K, float *grads, long long n_grads, float *stats,
+                          hipStream_t stream);
 int imk_launch_loss_finalize(const float *loss_partial, long long n_pix, int K, int kind, float *stats, hipStream_t stream);
 // consistency-loss step (imk_consist.hip): L = mean (pA - pB)^2 over two views' head outputs.  Fused (sigmoid heads, 1 or 3 maps on
 // 8 / 16 padded channels): head of both views + loss + both BatchNorm-output gradients with their statistics rows + one set of

@@ -397,7 +397,9 @@ __global__ __launch_bounds__(256) void head_kernel(const f16 *__restrict__ z, co
 // Same arithmetic as head_kernel followed by loss_grad_kernel (same expressions in the same order, so the values are
 // bit-identical), without the [n_pix, K] fp32 probability tensor in between: the logits are recomputed per pass
 // (K * CS FMAs) instead of being parked in HBM.
-template <int CS>
+// Y255 (loss kinds 2 / 3, continuous targets): the target is float32(y) / 255.0f, a correctly rounded divide (what
+// parse_image_depth_map forms); the other instantiation is the {0,1} code as it was.
+template <int CS, bool Y255 = false>
 __global__ __launch_bounds__(256) void head_loss_kernel(const f16 *__restrict__ z, const float *__restrict__ sc,
                                                         const float *__restrict__ sh, const float *__restrict__ w,
                                                         const float *__restrict__ bias, int cin, int K, int softmax,
@@ -445,7 +447,9 @@ __global__ __launch_bounds__(256) void head_loss_kernel(const f16 *__restrict__ 
                 for (int j = 0; j < 8; ++j) {
                     const int k = k0 + j;
                     if (k < K) {
-                        const float pk = 1.0f / (1.0f + expf(-logit(k))), t = (float)y[p * K + k];
+                        float t = (float)y[p * K + k];
+                        if constexpr (Y255) t = t / 255.0f;
+                        const float pk = 1.0f / (1.0f + expf(-logit(k)));
                         const float e = pk - t;
                         l += e * e;
                         g8[j] = (f16)(S * 2.0f * e * inv_n * pk * (1.0f - pk));
@@ -490,8 +494,8 @@ __global__ __launch_bounds__(256) void head_loss_kernel(const f16 *__restrict__ 
 // cce:  L = mean_{pixels} -log(p_t), dlogit_k = S * (p_k - [k == t]) / Npix   (softmax head; Keras takes the
 //       softmax ACTIVATION's cached logits, so there is no probability clipping in loss or gradient; p_t is only
 //       floored at FLT_MIN so that an fp32 underflow reports 87.3 instead of inf)
-__global__ __launch_bounds__(256) void loss_finalize_kernel(const float *__restrict__ partial, int n, double denom,
-                                                            float *__restrict__ stats) {
+// the partials' sum in the one fixed order both kernels below use (256 threads); the result is valid in every thread
+__device__ __forceinline__ double loss_partials_sum(const float *__restrict__ partial, int n) {
     __shared__ double r[256];
     double s = 0;
     for (int i0 = threadIdx.x; i0 < n; i0 += 8 * 256) {     // 8 independent loads in flight per thread; same summation order
@@ -507,7 +511,31 @@ __global__ __launch_bounds__(256) void loss_finalize_kernel(const float *__restr
         if (threadIdx.x < o) r[threadIdx.x] += r[threadIdx.x + o];
         __syncthreads();
     }
-    if (threadIdx.x == 0) stats[0] = (float)(r[0] / denom);   // stats[1..3]: head_loss_kernel and the gradient kernels
+    return r[0];
+}
+
+__global__ __launch_bounds__(256) void loss_finalize_kernel(const float *__restrict__ partial, int n, double denom,
+                                                            float *__restrict__ stats) {
+    const double tot = loss_partials_sum(partial, n);
+    if (threadIdx.x == 0) stats[0] = (float)(tot / denom);   // stats[1..3]: head_loss_kernel and the gradient kernels
+}
+
+// Loss kind 3, the reference's rmse (functions.py:36-37: sqrt(mean (p - y)^2)): d rmse / d. = d mse / d. * 0.5 / sqrt(mse), and every
+// gradient of the step is linear in the head's logit gradient, so the mse step's gradient vector is scaled once.  Every workgroup
+// forms mse from the loss partials itself, in loss_finalize_kernel's order (the float that kernel wrote to stats[0]); workgroup 0
+// then replaces stats[0] by the root -- nobody reads stats[0] here, so the order of the workgroups does not matter.  mse == 0 (or
+// NaN): s is inf (NaN), the gradients are no update; the overflow flag makes imk_unet_adamw_step skip the step, which is what Keras'
+// loss-scale optimizer does with the NaN gradient TensorFlow produces there.
+__global__ __launch_bounds__(256) void rmse_scale_kernel(const float *__restrict__ partial, int n, double denom,
+                                                         float *__restrict__ grads, long long n_grads, float *__restrict__ stats) {
+    const float mse = (float)(loss_partials_sum(partial, n) / denom);
+    const float root = sqrtf(mse);
+    const float s = 0.5f / root;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n_grads; i += (long long)gridDim.x * 256) grads[i] *= s;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        stats[0] = root;
+        if (!(mse > 0.f)) stats[1] = 1.0f;
+    }
 }
 
 // ---- optimizer --------------------------------------------------------------------------------------
@@ -880,14 +908,16 @@ int imk_loss_blocks(long long n_pix) {
 
 int imk_launch_head_loss(const f16 *z, const float *sc, const float *sh, const float *w, const float *bias, int cin, int cs,
                          int K, int softmax, long long n_pix, const uint8_t *y, const ImkCtl *ctl, float *stats,
-                         f16 *dlogit, float *loss_partial, hipStream_t stream) {
+                         f16 *dlogit, float *loss_partial, hipStream_t stream, int y255) {
     if (K > 64) return IMK_EUNSUPPORTED;
+    if (y255 && softmax) return IMK_EINVAL;
     const int nb = imk_loss_blocks(n_pix);
     const size_t lds = ((size_t)K * cs + K + 2 * cs + (softmax ? 256 * (size_t)(K | 1) : 0)) * sizeof(float);
     const int cs_out = imk_pad8(K);
     ImkProfScope prof(PF_HEAD_LOSS, (double)n_pix * (cs * 2 + (softmax ? 1 : K) + cs_out * 2), stream);
-#define IMK_HL(CS) if (lds > 64 * 1024) IMK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(head_loss_kernel<CS>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-    imk_klaunch(head_loss_kernel<CS>, dim3(nb), dim3(256), lds, stream, z, sc, sh, w, bias, cin, K, softmax, n_pix, y, ctl, stats, cs_out, dlogit, loss_partial)
+#define IMK_HL1(KERN) do { if (lds > 64 * 1024) IMK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(KERN), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+    imk_klaunch(KERN, dim3(nb), dim3(256), lds, stream, z, sc, sh, w, bias, cin, K, softmax, n_pix, y, ctl, stats, cs_out, dlogit, loss_partial); } while (0)
+#define IMK_HL(CS) if (y255) IMK_HL1((head_loss_kernel<CS, true>)); else IMK_HL1((head_loss_kernel<CS>))
     switch (cs) {
         case 8: IMK_HL(8); break;
         case 16: IMK_HL(16); break;
@@ -896,6 +926,7 @@ int imk_launch_head_loss(const f16 *z, const float *sc, const float *sh, const f
         default: return IMK_EUNSUPPORTED;
     }
 #undef IMK_HL
+#undef IMK_HL1
     IMK_LAUNCH_CHECK();
     return IMK_OK;
 }
@@ -905,6 +936,17 @@ int imk_launch_loss_finalize(const float *loss_partial, long long n_pix, int K, 
     const double denom = kind == 0 ? (double)n_pix * K : (double)n_pix;
     ImkProfScope prof(PF_STEP_TAIL, (double)imk_loss_blocks(n_pix) * 4, stream);
     imk_klaunch(loss_finalize_kernel, dim3(1), dim3(256), 0, stream, loss_partial, imk_loss_blocks(n_pix), denom, stats);
+    IMK_LAUNCH_CHECK();
+    return IMK_OK;
+}
+
+int imk_launch_rmse_scale(const float *loss_partial, long long n_pix, int K, float *grads, long long n_grads, float *stats,
+                          hipStream_t stream) {
+    ImkProfScope prof(PF_STEP_TAIL, (double)n_grads * 8, stream);
+    long long nb = (n_grads + 1023) / 1024;      // 4 elements per thread; every workgroup repeats the (<= 1024-element) reduction
+    if (nb < 1) nb = 1;
+    if (nb > 1024) nb = 1024;
+    imk_klaunch(rmse_scale_kernel, dim3((int)nb), dim3(256), 0, stream, loss_partial, imk_loss_blocks(n_pix), (double)n_pix * K, grads, n_grads, stats);
     IMK_LAUNCH_CHECK();
     return IMK_OK;
 }

@@ -220,6 +220,22 @@ struct ImkHeadImArgs {
 bool imk_head_im_supported(const ImkHeadImArgs &a);
 int imk_launch_head_im(const ImkHeadImArgs &a, hipStream_t stream);
 
+// ---- fused head + standard-deviation map of the depth-map IM (imk_depth.hip) ------------------------------------------------
+struct ImkDepthHeadArgs {
+    const f16 *z[IMK_HEAD_IM_MAX_MODELS];        // last decoder block's conv output [B,H,W,cs] of every model
+    const float *sc[IMK_HEAD_IM_MAX_MODELS], *sh[IMK_HEAD_IM_MAX_MODELS];   // its folded BatchNorm
+    const float *w[IMK_HEAD_IM_MAX_MODELS], *bias[IMK_HEAD_IM_MAX_MODELS];  // the head's fp32 kernel [cin][1] / bias [1]
+    int n_models, cin, cs, K, softmax;
+    int batch, hw;
+    float *map;                                  // [B,H,W] fp32: the per-pixel standard deviation over the models
+};
+// Sigmoid heads with one map, last decoder widths 8 / 16 / 24 / 32, 2 .. 8 models, H*W a multiple of 16, a 16-byte aligned map.
+bool imk_depth_head_supported(const ImkDepthHeadArgs &a);
+int imk_launch_depth_head_std(const ImkDepthHeadArgs &a, hipStream_t stream);
+// launches 2 and 3 of imk_im_depth on a finished map (image thresholds, then mask + blocking + sizes)
+int imk_depth_finish(const float *map, int batch, int hw, float mult, const uint8_t *img, int c, int block_in, uint8_t *img_out,
+                     uint8_t *im_out, int64_t *im_size, float *thr_out, hipStream_t stream);
+
 // ---- fused head + model-ensemble vote (imk_vote.hip) ----------------------------------------------------------------------
 struct ImkVoteHeadArgs {
     const f16 *z[IMK_HEAD_IM_MAX_MODELS];        // last decoder block's conv output [B,H,W,cs] of every model

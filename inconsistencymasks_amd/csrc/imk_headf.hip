@@ -308,7 +308,8 @@ __global__ __launch_bounds__(256) void head_cce_fused_kernel(HeadCceArgs a) {
 // its BatchNorm-backward statistics, and the output layer's weight / bias gradient -- z read once, dy written once.
 // Per-thread fp32 accumulators, reduced per workgroup in a fixed order into the partial-row layouts the other producers use
 // (bn_bwd_coef_kernel, wgf_stage1_kernel): bit-reproducible.
-template <int CS, int K>
+// Y255 (loss kinds 2 / 3): targets float32(y) / 255.0f, as head_loss_kernel's; the other instantiation is the {0,1} code as it was.
+template <int CS, int K, bool Y255 = false>
 __global__ __launch_bounds__(256) void head_mse_fused_kernel(HeadCceArgs a) {
     IMK_STAMP_BEGIN(headf, 90000);
     constexpr int NA = 2 * CS + CS * K + K + 1;      // sum dy | sum dy z | dW[c][k] | db[k] | loss
@@ -344,7 +345,9 @@ __global__ __launch_bounds__(256) void head_mse_fused_kernel(HeadCceArgs a) {
             float lg = s_b[k];
 #pragma unroll
             for (int c = 0; c < CS; ++c) lg += xin[c] * s_w[k * CS + c];
-            const float pk = 1.0f / (1.0f + expf(-lg)), e = pk - (float)yv[k];
+            float tk = (float)yv[k];
+            if constexpr (Y255) tk = tk / 255.0f;
+            const float pk = 1.0f / (1.0f + expf(-lg)), e = pk - tk;
             acc[2 * CS + CS * K + K] += e * e;
             gk[k] = (float)(f16)(S * 2.0f * e * inv_n * pk * (1.0f - pk));
             acc[2 * CS + CS * K + k] += gk[k];
@@ -427,11 +430,12 @@ bool imk_head_mse_fused_ok(int cs, int K, long long n_pix, int rows_cap) {
 
 int imk_launch_head_mse_fused(const f16 *z, const float *sc, const float *sh, const float *w, const float *bias, int cin, int cs,
                               int K, long long n_pix, const uint8_t *y, const ImkCtl *ctl, float *stats, f16 *dy,
-                              float *loss_partial, float *dystat_partial, float *wg_partial, hipStream_t stream) {
+                              float *loss_partial, float *dystat_partial, float *wg_partial, hipStream_t stream, int y255) {
     HeadCceArgs a{z, sc, sh, w, bias, cin, cs, K, n_pix, y, ctl, stats, dy, loss_partial, dystat_partial, wg_partial, 1};
     const int grid = imk_loss_blocks(n_pix);
     ImkProfScope prof(PF_HEAD_LOSS, (double)n_pix * (cs * 2 + K + cs * 2), stream, 6.0 * n_pix * cin * K);
-    if (cs == 8 && K == 1) imk_klaunch(head_mse_fused_kernel<8, 1>, dim3(grid), dim3(256), 0, stream, a);
+    if (cs == 8 && K == 1 && y255) imk_klaunch(head_mse_fused_kernel<8, 1, true>, dim3(grid), dim3(256), 0, stream, a);
+    else if (cs == 8 && K == 1) imk_klaunch(head_mse_fused_kernel<8, 1>, dim3(grid), dim3(256), 0, stream, a);
     else return IMK_EUNSUPPORTED;
     IMK_LAUNCH_CHECK();
     return IMK_OK;

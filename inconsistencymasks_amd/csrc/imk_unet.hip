@@ -416,6 +416,52 @@ extern "C" int imk_unet_forward_im(const imk_unet_plan *plan, int n_models, cons
                              img_out, masks_out, im_out, im_size, presence, stream_);
 }
 
+// Ensemble inference + the depth-map family's standard-deviation IM.  Workspace: [the std map, B*H*W fp32 | imk_unet_forward_im's
+// workspace]: the model loop of imk_unet_forward_im, then the fused head + std kernel on the activation slabs (imk_depth.hip), or --
+// for the shapes it does not cover -- imk_im_depth's first launch on the probability stack; the thresholds and the mask either way.
+static size_t depth_map_bytes(const imk_unet_plan *plan, int batch) {
+    return up((size_t)batch * plan->cfg.h * plan->cfg.w * sizeof(float));
+}
+
+extern "C" int64_t imk_unet_forward_im_depth_workspace_bytes(const imk_unet_plan *plan, int n_models, int batch, int n_streams) {
+    const int64_t fwd = imk_unet_forward_im_workspace_bytes(plan, n_models, batch, n_streams);
+    return fwd < 0 ? fwd : fwd + (int64_t)depth_map_bytes(plan, batch);
+}
+
+extern "C" int imk_unet_forward_im_depth(const imk_unet_plan *plan, int n_models, const float *const *params,
+                                         const void *const *packed, const uint8_t *x, int batch, float mult, const uint8_t *img,
+                                         int block_in, uint8_t *img_out, uint8_t *im_out, int64_t *im_size, float *thr_out,
+                                         float *std_out, void *workspace, int64_t workspace_bytes, void *stream_) {
+    IMK_CHECK_ARG(plan && plan->net == 0 && params && packed && x && workspace && batch > 0);
+    IMK_CHECK_ARG(im_out && im_size && thr_out && (!img || img_out));
+    const imk_unet_cfg &cf = plan->cfg;
+    if (n_models < 2 || n_models > 16 || cf.act_out != 0 || cf.n_out != 1 || batch > 65535) return IMK_EUNSUPPORTED;
+    const Ws ws = make_ws(plan, batch, 0);
+    const Topo topo = make_topo(plan);
+    const size_t map_bytes = depth_map_bytes(plan, batch);
+    uint8_t *base = (uint8_t *)workspace + map_bytes;
+    const int64_t fwd_bytes = workspace_bytes - (int64_t)map_bytes;
+    float *map = std_out ? std_out : (float *)workspace;
+    ImkDepthHeadArgs da{};
+    da.n_models = n_models; da.cin = cf.ch[0]; da.cs = imk_pad8(cf.ch[0]); da.K = cf.n_out; da.softmax = cf.act_out;
+    da.batch = batch; da.hw = cf.h * cf.w; da.map = map;
+    const bool fused = !plan->dbg_materialize && imk_depth_head_supported(da) &&
+                       (int64_t)(head_slab_bytes(plan, batch, true) * n_models + ws.total) <= fwd_bytes;
+    const size_t slab = head_slab_bytes(plan, batch, fused);
+    if (fwd_bytes < 0 || (int64_t)(slab * n_models + ws.total) > fwd_bytes) return IMK_EWORKSPACE;
+    hipStream_t main_stream = (hipStream_t)stream_;
+    const EnsembleHeads heads{da.z, da.sc, da.sh, da.w, da.bias};
+    int rc = run_ensemble_forwards(plan, topo, ws, n_models, params, packed, x, batch, slab, base, fwd_bytes,
+                                   fused ? &heads : nullptr, main_stream);
+    if (rc) return rc;
+    if (!fused)      // the stack [N,B,H,W] at the start of the slabs; its map is `map` (never the workspace imk_im_depth would take)
+        return imk_im_depth((const float *)base, n_models, batch, cf.h, cf.w, mult, img, cf.c_in, block_in, img_out, im_out, im_size,
+                            thr_out, map, nullptr, 0, stream_);
+    rc = imk_launch_depth_head_std(da, main_stream);
+    if (rc) return rc;
+    return imk_depth_finish(map, batch, da.hw, mult, img, cf.c_in, block_in, img_out, im_out, im_size, thr_out, main_stream);
+}
+
 // Ensemble inference + model-ensemble vote: the model loop of imk_unet_forward_im, then the fused head + vote kernel
 // (imk_vote.hip) on the activation slabs, or -- for the shapes it does not cover -- imk_vote_* on the probability stack.
 // Workspace: imk_unet_forward_im_workspace_bytes.
@@ -731,8 +777,10 @@ extern "C" int imk_unet_fwd_bwd(const imk_unet_plan *plan, float *params, void *
                                 const uint8_t *y, int batch, int loss_kind, float *grads, float *stats, void *workspace,
                                 int64_t workspace_bytes, void *stream_) {
     IMK_CHECK_ARG(plan && params && packed && state && x && y && grads && stats && workspace && batch > 0);
-    IMK_CHECK_ARG(loss_kind == 0 || loss_kind == 1);
-    IMK_CHECK_ARG((loss_kind == 0) == (plan->cfg.act_out == 0));  // mse <-> sigmoid head, cce <-> softmax head
+    IMK_CHECK_ARG(loss_kind >= 0 && loss_kind <= 3);
+    IMK_CHECK_ARG((loss_kind != 1) == (plan->cfg.act_out == 0));  // mse / rmse <-> sigmoid head, cce <-> softmax head
+    const int y255 = loss_kind >= 2;                              // kinds 2, 3: continuous targets y / 255.0f
+    const int fin_kind = loss_kind == 1 ? 1 : 0;                  // the loss finalize's denominator: every element, or every pixel
     hipStream_t stream = (hipStream_t)stream_;
     Ctx c{plan, make_ws(plan, batch, 1), (uint8_t *)workspace, params, (const uint8_t *)packed, batch, true, stream};
     if ((int64_t)c.ws.total > workspace_bytes) return IMK_EWORKSPACE;
@@ -759,7 +807,7 @@ extern "C" int imk_unet_fwd_bwd(const imk_unet_plan *plan, float *params, void *
     const bool head_mse_pass = cf.act_out == 0 && imk_head_mse_fused_ok(imk_pad8(ol.cin), ol.cout, n_pix, c.ws.L[obn].n_bwd_rows);
     if (!head_one_pass && !head_mse_pass)
         OK(imk_launch_head_loss(c.act(t.d_c1[3]), c.bn_scale(obn), c.bn_shift(obn), params + ol.off_w, params + ol.off_b, ol.cin,
-                                imk_pad8(ol.cin), ol.cout, cf.act_out, n_pix, y, sv.ctl, stats, dlogit, loss_partial, stream));
+                                imk_pad8(ol.cin), ol.cout, cf.act_out, n_pix, y, sv.ctl, stats, dlogit, loss_partial, stream, y255));
 
     // The weight-gradient kernels run on a side stream, forked after the kernel that produced their gradient operand and
     // joined before the final reduction: nothing on the backward chain depends on them, and they fill the gaps that the
@@ -771,9 +819,9 @@ extern "C" int imk_unet_fwd_bwd(const imk_unet_plan *plan, float *params, void *
     ImkStopRingScope stop_ring(plan, stream, b.n_side);      // from here on: the backward pass's launches carry their own events
     bool loss_done = false;
     auto loss_on_side = [&]() -> int {      // once, as soon as a fork exists (every fork event is younger than the head's kernel)
-        if (loss_done || b.n_side <= 0 || b.n_fork <= 0) return IMK_OK;
+        if (loss_done || b.n_side <= 0 || b.n_fork <= 0 || loss_kind == 3) return IMK_OK;      // kind 3: on `stream`, in front of its scaling launch
         loss_done = true;
-        return imk_launch_loss_finalize(loss_partial, n_pix, cf.n_out, loss_kind, stats, plan->side[(b.n_fork - 1) % b.n_side]);
+        return imk_launch_loss_finalize(loss_partial, n_pix, cf.n_out, fin_kind, stats, plan->side[(b.n_fork - 1) % b.n_side]);
     };
     int head_rows = 0;
     HeadWgJob head_job{};
@@ -782,7 +830,7 @@ extern "C" int imk_unet_fwd_bwd(const imk_unet_plan *plan, float *params, void *
         float *wgp = reinterpret_cast<float *>(c.base + c.ws.L[t.out].wg_partial);
         OK(imk_launch_head_mse_fused(c.act(t.d_c1[3]), c.bn_scale(obn), c.bn_shift(obn), params + ol.off_w, params + ol.off_b,
                                      ol.cin, imk_pad8(ol.cin), ol.cout, n_pix, y, sv.ctl, stats, c.dy(obn), loss_partial,
-                                     reinterpret_cast<float *>(c.base + c.ws.L[obn].bwd_partial), wgp, stream));
+                                     reinterpret_cast<float *>(c.base + c.ws.L[obn].bwd_partial), wgp, stream, y255));
         head_rows = rows;
         head_job = HeadWgJob{wgp, rows};
     } else if (head_one_pass) {
@@ -797,7 +845,12 @@ extern "C" int imk_unet_fwd_bwd(const imk_unet_plan *plan, float *params, void *
         OK(head_dgrad(b, t, dlogit, loss_on_side, &head_rows, &head_job));
     }
     OK(run_backward(b, t, head_rows, head_job.partial ? &head_job : nullptr, loss_on_side));
-    if (!loss_done) OK(imk_launch_loss_finalize(loss_partial, n_pix, cf.n_out, loss_kind, stats, stream));
+    if (!loss_done) OK(imk_launch_loss_finalize(loss_partial, n_pix, cf.n_out, fin_kind, stats, stream));
+    if (loss_kind == 3) {      // rmse: the mse step's gradients times 0.5 / sqrt(mse), behind the finalize and every gradient's reduction
+        int64_t n_total = 0, n_train = 0;
+        OK(imk_unet_param_count(plan, &n_total, &n_train));
+        OK(imk_launch_rmse_scale(loss_partial, n_pix, cf.n_out, grads, n_train, stats, stream));
+    }
 #undef OK
     return IMK_OK;
 }

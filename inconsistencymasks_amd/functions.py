@@ -1881,3 +1881,6 @@ from .evalnet_functions import (compute_classwise_detection, compute_classwise_d
                                 train_evalnet_miou_model_multiclass)
 from .consistency import (train_hela_consistency_loss, train_ISIC_2018_consistency_loss,  # noqa: E402,F401
                           train_multiclass_consistency_loss)
+# the depth-map (regression) family (functions.py:36-48, 320-364, 903-927, 1051-1073, 1345-1384, 6155-6177)
+from .depth import (benchmark_depth_map, delta_metric, get_im_prediction_depth_map, load_labeled_data_depth_map,  # noqa: E402,F401
+                    parse_image_depth_map, rmse, train_depth_map)
