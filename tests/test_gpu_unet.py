@@ -116,6 +116,23 @@ def randomize_bn(sd, seed):
     return sd
 
 
+def assert_layer_bound(got, tap, what):
+    """the bound of test_inference_parity on one stored conv output against the fp16-emulating oracle's tap"""
+    assert rel_l2(got, tap) <= 1e-2, what
+
+
+def assert_probability_bounds(probs, ref, act):
+    """the bounds of test_inference_parity on probabilities against the fp16-emulating oracle's"""
+    assert np.abs(probs - ref).max() <= 3e-2
+    assert rel_l2(probs, ref) <= 1e-2
+    if act == "softmax":
+        assert np.allclose(probs.sum(-1), 1.0, atol=1e-5)
+        flips = (probs.argmax(-1) != ref.argmax(-1)).mean()
+    else:
+        flips = ((probs > 0.5) != (ref > 0.5)).mean()
+    assert flips <= 0.01, f"decision flip rate {flips}"
+
+
 @pytest.mark.parametrize("name", list(CFGS))
 def test_inference_parity(UNet, name):
     cfg = CFGS[name]
@@ -135,7 +152,7 @@ def test_inference_parity(UNet, name):
         for l in m.plan.layers:
             if l["kind"] == 0 and l["name"] != "out":
                 got = m.intermediate(l["name"], cfg["b"], 0).numpy()
-                assert rel_l2(got, taps[l["name"]].numpy()) <= 1e-2, l["name"]
+                assert_layer_bound(got, taps[l["name"]].numpy(), l["name"])
     finally:
         m.debug(materialize=False)
     # (2) the default path -- what bench.py and the writers run: the input block is computed on load by the first encoder
@@ -145,21 +162,14 @@ def test_inference_parity(UNet, name):
     for l in m.plan.layers:
         if l["kind"] == 0 and (l["name"].endswith(".c1") or l["name"].endswith(".ca")):
             got = m.intermediate(l["name"], cfg["b"], 0).numpy()
-            assert rel_l2(got, taps[l["name"]].numpy()) <= 1e-2, "default path: " + l["name"]
+            assert_layer_bound(got, taps[l["name"]].numpy(), "default path: " + l["name"])
     stem_on_load = cfg["c"] <= 4 and int(16 * cfg["alpha"]) <= 16       # imk_conv_stem_fusable
     if stem_on_load:    # same fp16 roundings, fp32 sums of <= 4 products in another order (test_fused_input_block_...)
         assert np.abs(probs - probs_stored).max() <= 2e-3
     else:               # only the chaining differs: the intermediate's fp16 rounding happens on chip, bit-identical
         assert np.array_equal(probs, probs_stored)
     assert np.abs(probs_stored - ref).max() <= 3e-2 and rel_l2(probs_stored, ref) <= 1e-2
-    assert np.abs(probs - ref).max() <= 3e-2
-    assert rel_l2(probs, ref) <= 1e-2
-    if cfg["act"] == "softmax":
-        assert np.allclose(probs.sum(-1), 1.0, atol=1e-5)
-        flips = (probs.argmax(-1) != ref.argmax(-1)).mean()
-    else:
-        flips = ((probs > 0.5) != (ref > 0.5)).mean()
-    assert flips <= 0.01, f"decision flip rate {flips}"
+    assert_probability_bounds(probs, ref, cfg["act"])
     # predict() (numpy in / numpy out, batches) is the same computation
     assert np.array_equal(m.predict([x], batch_size=3), probs)
     # the independent fp32 oracle: randomised BatchNorm parameters (this model) and default initialisation
@@ -243,6 +253,12 @@ def train_step_parity(UNet, cfg, batch=None):
         scale = float(stats[2]) / 2
         assert scale >= 1.0
         m.load_state_dict(sd)          # undo the moving-statistics update
+    assert_step_bounds(m, stats, g1, moving_after_1, loss_ref, grads_ref, sd_ref)
+
+
+def assert_step_bounds(m, stats, g1, moving_after_1, loss_ref, grads_ref, sd_ref):
+    """the bounds of train_step_parity on one GPU step (its stats, gradients and state dict after the step) against the oracle's loss,
+    gradients and state dict after its step"""
     assert abs(stats[0] - loss_ref) <= 1e-4 * max(1.0, abs(loss_ref))
     g = g1.cpu()
     errs = {}
