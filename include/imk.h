@@ -244,6 +244,16 @@ IMK_API int imk_unet_forward_vote(const imk_unet_plan *plan, int n_models,
  *                 sqrtf(mse).  A batch with mse == 0 sets the overflow flag stats[1] and is skipped by imk_unet_adamw_step (Keras'
  *                 loss-scale optimizer skips the NaN gradient TensorFlow produces there).  A rank's rmse is not the batch's: do
  *                 not average kind-3 gradients over data-parallel ranks.
+ *             4 = the reference's dice_loss (functions.py:162-184, smooth = 1) on the targets of kind 0, t = float(y) (HeLa's position
+ *                 plane is 0 / 3); sigmoid heads only, a softmax plan is an argument error.  Per image b of the batch, over its
+ *                 H*W*n_out elements: I_b = sum t p, U_b = sum t + sum p, dice_b = (2 I_b + 1) / (U_b + 1), loss = 1 - mean_b dice_b,
+ *                 d loss / d p = c0_b - c1_b t with c0_b = (2 I_b + 1) / (B (U_b + 1)^2), c1_b = 2 / (B (U_b + 1)).  Three launches
+ *                 in order on `stream`: the per-image sums (fp32 per thread, fixed-order partial rows in the workspace), one
+ *                 workgroup that adds them in double and writes the coefficients and stats[0], and the gradient pass, which
+ *                 recomputes the probabilities (no atomics: bit-reproducible; nothing depends on what the workspace held).  The
+ *                 gradient pass is one fused kernel for 8 padded channels and 1 map; IMK_DICE_FUSED=0 forces the general route
+ *                 (logit gradient, then the output layer's dgrad).  Every rank's loss is a mean over its own images: with equal
+ *                 batch sizes, averaging kind-4 gradients over data-parallel ranks is the batch's gradient.
  *   grads     [trainable] float32, UNSCALED gradient of the mean loss
  *   stats     device float[4]: {loss, found_inf (0/1), loss_scale used, reserved}
  *   state     device buffer of imk_unet_state_bytes(): Adam m, v, step counter, dynamic loss scale
@@ -418,6 +428,13 @@ IMK_API int imk_eval_multiclass(const float *probs, const uint8_t *gt, int batch
  * out: device buffer of imk_eval_soft_out_doubles(K) doubles (results first, block partials behind them); K <= 64. */
 IMK_API int64_t imk_eval_soft_out_doubles(int k);
 IMK_API int imk_eval_soft_sums(const float *probs, const uint8_t *gt, int64_t n_pix, int k, int mode, double *out, void *stream);
+
+/* The sums of the reference's dice_loss (functions.py:162-184) per image: probs [B,H,W,K] f32, gt [B,H,W,K] u8 targets ->
+ * out [B,3] double = (sum t p, sum t, sum p) with t = double(gt).  One workgroup per image, double accumulators in an order fixed
+ * by H*W*K alone: an image's row does not depend on the batch it is in.  The loss of a prediction is
+ * 1 - mean_b (2 out[b][0] + 1) / (out[b][1] + out[b][2] + 1); train_hela's val_loss monitor under dice_loss is that over all
+ * validation images. */
+IMK_API int imk_eval_dice_sums(const float *probs, const uint8_t *gt, int batch, int h, int w, int k, double *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Depth-map (regression) family (csrc/imk_depth.hip): get_im_prediction_depth_map (functions.py:6155-6177), benchmark_depth_map

@@ -40,7 +40,19 @@ int imk_launch_head_cce_fused(const f16 *z, const float *sc, const float *sh, co
 bool imk_head_mse_fused_ok(int cs, int K, long long n_pix, int rows_cap);
 int imk_launch_head_mse_fused(const f16 *z, const float *sc, const float *sh, const float *w, const float *bias, int cin, int cs,
                               int K, long long n_pix, const uint8_t *y, const ImkCtl *ctl, float *stats, f16 *dy,
-                              float *loss_partial, float *dystat_partial, float *wg_partial, hipStream_t stream, int y255 = 0);
+                              float *loss_partial, float *dystat_partial, float *wg_partial, hipStream_t stream, int y255 = 0,
+                              const float *dice_coef = nullptr, int hw = 0);   // dice_coef: the Dice variant (loss kind 4), see below
+// loss kind 4, the reference's dice_loss on sigmoid heads (imk_dice.hip): per-image sums (rows = imk_dice_rows(batch, hw) partial rows
+// of 3 floats per image; sets stats[1..3] like head_loss_kernel), then the images' coefficients coef [batch][2], their Dice values
+// dice [batch] and stats[0] = the loss, then the fp16 logit gradient in head_loss_kernel's layout (or imk_launch_head_mse_fused with
+// dice_coef where imk_head_mse_fused_ok)
+int imk_dice_rows(int batch, int hw);
+int imk_launch_dice_sums(const f16 *z, const float *sc, const float *sh, const float *w, const float *bias, int cin, int cs, int K,
+                         int batch, int hw, const uint8_t *y, const ImkCtl *ctl, float *stats, float *partial, hipStream_t stream);
+int imk_launch_dice_coef(const float *partial, int batch, int hw, float *coef, double *dice, float *stats, hipStream_t stream);
+int imk_launch_dice_dlogit(const f16 *z, const float *sc, const float *sh, const float *w, const float *bias, int cin, int cs, int K,
+                           long long n_pix, int hw, const uint8_t *y, const ImkCtl *ctl, const float *coef, f16 *dlogit,
+                           hipStream_t stream);
 // loss kind 3 (the reference's rmse = sqrt(mse)), behind the mse step's loss finalize: every gradient is linear in the head's logit
 // gradient, so grads[i] *= 0.5f / sqrtf(mse) and stats[0] = sqrtf(mse); mse == 0 sets the overflow flag stats[1] (the step is skipped)
 int imk_launch_rmse_scale(const float *loss_partial, long long n_pix, int K, float *grads, long long n_grads, float *stats,

@@ -37,6 +37,19 @@ __device__ __forceinline__ void head_input(const f16 *__restrict__ z, long long 
     }
 }
 
+// the same from activation vectors the caller loaded itself (several pixels' loads in flight before the first one's arithmetic)
+template <int CS>
+__device__ __forceinline__ void head_input_regs(const f16x8 (&v)[CS / 8], const float *s_w, int K, float (&xin)[CS]) {
+    const float *s_sc = s_w + K * CS + K, *s_sh = s_sc + CS;
+#pragma unroll
+    for (int q = 0; q < CS / 8; ++q)
+#pragma unroll
+        for (int j = 0; j < 8; j += 2) {
+            const f16x2 r2 = imk_affine2(f16x2{v[q][j], v[q][j + 1]}, f32x2{s_sc[q * 8 + j], s_sc[q * 8 + j + 1]}, f32x2{s_sh[q * 8 + j], s_sh[q * 8 + j + 1]});
+            xin[q * 8 + j] = (float)r2[0]; xin[q * 8 + j + 1] = (float)r2[1];
+        }
+}
+
 template <int CS>
 __device__ __forceinline__ float head_logit(const float (&xin)[CS], const float *s_w, int K, int k) {
     float acc = s_w[K * CS + k];
@@ -46,6 +59,17 @@ __device__ __forceinline__ float head_logit(const float (&xin)[CS], const float 
 }
 
 __device__ __forceinline__ float head_sigmoid(float logit) { return 1.0f / (1.0f + expf(-logit)); }
+
+// ---- Dice loss (loss kind 4; imk_dice.hip and head_mse_fused_kernel's Dice variant) ----------------------------------------------
+// image of pixel p of a [B][hw] batch (one 32-bit divide wherever the pixel index fits)
+__device__ __forceinline__ int dice_image(long long p, int hw) {
+    return (p >> 32) ? (int)(p / hw) : (int)((unsigned)p / (unsigned)hw);
+}
+// d(loss * scale)/d(logit) of an element with target t and probability pk of an image with coefficients (c0, c1): the ONE
+// expression of both gradient kernels, so that the routes differ by their dgrad alone
+__device__ __forceinline__ float dice_dlogit(float S, float c0, float c1, float t, float pk) {
+    return S * (c0 - c1 * t) * (pk * (1.0f - pk));
+}
 
 // softmax over the K classes into row[0..K) (an LDS row of the caller)
 template <int CS>

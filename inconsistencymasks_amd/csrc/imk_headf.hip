@@ -21,6 +21,7 @@
 //       image [tile][pixel][16] and come back with transposed reads (the weight-gradient kernels' pattern).
 // Fixed reduction orders everywhere (per-wave accumulators -> per-workgroup partial rows): bit-reproducible.
 #include "imk_stage.h"
+#include "imk_head.h"
 
 IMK_STAMP_TABLE(headf)
 
@@ -40,6 +41,8 @@ struct HeadCceArgs {
     float *dystat_partial;        // [grid][2 * CS]: sum dy, sum dy * z per channel
     float *wg_partial;            // [grid][NCT * cot_n][2][256]: weight-gradient partials in wgf_stage1's layout
     int cot_n;                    // 16-class tiles of the weight-gradient layout = ceil(pad8(K) / 16)
+    const float *dice_coef;       // head_mse_fused_kernel's Dice variant: (c0, c1) per image [n_pix / hw][2] (imk_dice.hip)
+    int hw;                       // ... and the pixels per image
 };
 
 template <int CS, int KT>
@@ -309,7 +312,10 @@ __global__ __launch_bounds__(256) void head_cce_fused_kernel(HeadCceArgs a) {
 // Per-thread fp32 accumulators, reduced per workgroup in a fixed order into the partial-row layouts the other producers use
 // (bn_bwd_coef_kernel, wgf_stage1_kernel): bit-reproducible.
 // Y255 (loss kinds 2 / 3): targets float32(y) / 255.0f, as head_loss_kernel's; the other instantiation is the {0,1} code as it was.
-template <int CS, int K, bool Y255 = false>
+// DICE (loss kind 4): the logit gradient is dice_dlogit's with the image's coefficients, which dice_coef_kernel formed from the
+// sums launch (imk_dice.hip); the loss value is that kernel's, so no loss partial is accumulated or written.  The other
+// instantiations are the code they were.
+template <int CS, int K, bool Y255 = false, bool DICE = false>
 __global__ __launch_bounds__(256) void head_mse_fused_kernel(HeadCceArgs a) {
     IMK_STAMP_BEGIN(headf, 90000);
     constexpr int NA = 2 * CS + CS * K + K + 1;      // sum dy | sum dy z | dW[c][k] | db[k] | loss
@@ -340,6 +346,8 @@ __global__ __launch_bounds__(256) void head_mse_fused_kernel(HeadCceArgs a) {
             xin[c] = (float)imk_affine1(zv[c >> 3][c & 7], s_sc[c], s_sh[c]);
         }
         float gk[K];
+        float c0 = 0.f, c1 = 0.f;
+        if constexpr (DICE) { const int b = dice_image(p, a.hw); c0 = a.dice_coef[2 * b]; c1 = a.dice_coef[2 * b + 1]; }
 #pragma unroll
         for (int k = 0; k < K; ++k) {
             float lg = s_b[k];
@@ -348,8 +356,12 @@ __global__ __launch_bounds__(256) void head_mse_fused_kernel(HeadCceArgs a) {
             float tk = (float)yv[k];
             if constexpr (Y255) tk = tk / 255.0f;
             const float pk = 1.0f / (1.0f + expf(-lg)), e = pk - tk;
-            acc[2 * CS + CS * K + K] += e * e;
-            gk[k] = (float)(f16)(S * 2.0f * e * inv_n * pk * (1.0f - pk));
+            if constexpr (DICE) {
+                gk[k] = (float)(f16)dice_dlogit(S, c0, c1, tk, pk);
+            } else {
+                acc[2 * CS + CS * K + K] += e * e;
+                gk[k] = (float)(f16)(S * 2.0f * e * inv_n * pk * (1.0f - pk));
+            }
             acc[2 * CS + CS * K + k] += gk[k];
         }
         f16x8 dv[CS / 8];
@@ -405,7 +417,8 @@ __global__ __launch_bounds__(256) void head_mse_fused_kernel(HeadCceArgs a) {
     __syncthreads();
     auto tot = [&](int i) { return (s_red[0][i] + s_red[1][i]) + (s_red[2][i] + s_red[3][i]); };
     if (t < 2 * CS) a.dystat_partial[(size_t)blockIdx.x * 2 * CS + t] = tot(t);
-    if (t == 0) a.loss_partial[blockIdx.x] = tot(2 * CS + CS * K + K);
+    if constexpr (!DICE)
+        if (t == 0) a.loss_partial[blockIdx.x] = tot(2 * CS + CS * K + K);
     // weight-gradient partial row [tap 0 | bias][256] in wgf_stage1's layout: element e = r * 64 + l holds (ci = 4 (l >> 4) + r,
     // co = l & 15); the bias row keeps co in elements 0..15
     float *wp = a.wg_partial + (size_t)blockIdx.x * 2 * 256;
@@ -430,11 +443,14 @@ bool imk_head_mse_fused_ok(int cs, int K, long long n_pix, int rows_cap) {
 
 int imk_launch_head_mse_fused(const f16 *z, const float *sc, const float *sh, const float *w, const float *bias, int cin, int cs,
                               int K, long long n_pix, const uint8_t *y, const ImkCtl *ctl, float *stats, f16 *dy,
-                              float *loss_partial, float *dystat_partial, float *wg_partial, hipStream_t stream, int y255) {
-    HeadCceArgs a{z, sc, sh, w, bias, cin, cs, K, n_pix, y, ctl, stats, dy, loss_partial, dystat_partial, wg_partial, 1};
+                              float *loss_partial, float *dystat_partial, float *wg_partial, hipStream_t stream, int y255,
+                              const float *dice_coef, int hw) {
+    HeadCceArgs a{z, sc, sh, w, bias, cin, cs, K, n_pix, y, ctl, stats, dy, loss_partial, dystat_partial, wg_partial, 1, dice_coef, hw};
+    if (dice_coef && (y255 || hw <= 0)) return IMK_EINVAL;
     const int grid = imk_loss_blocks(n_pix);
     ImkProfScope prof(PF_HEAD_LOSS, (double)n_pix * (cs * 2 + K + cs * 2), stream, 6.0 * n_pix * cin * K);
-    if (cs == 8 && K == 1 && y255) imk_klaunch(head_mse_fused_kernel<8, 1, true>, dim3(grid), dim3(256), 0, stream, a);
+    if (cs == 8 && K == 1 && dice_coef) imk_klaunch(head_mse_fused_kernel<8, 1, false, true>, dim3(grid), dim3(256), 0, stream, a);
+    else if (cs == 8 && K == 1 && y255) imk_klaunch(head_mse_fused_kernel<8, 1, true>, dim3(grid), dim3(256), 0, stream, a);
     else if (cs == 8 && K == 1) imk_klaunch(head_mse_fused_kernel<8, 1>, dim3(grid), dim3(256), 0, stream, a);
     else return IMK_EUNSUPPORTED;
     IMK_LAUNCH_CHECK();

@@ -91,6 +91,7 @@ struct Ws {
     size_t dP[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // train: gradient w.r.t. the pooled output of a block (U-Net: encoder i+1;
                                                // EvalNet: trunk block i+1, [5] = the last block's, written by the head)
     size_t probs = 0, dlogit = 0, loss_partial = 0;
+    size_t dice_partial = 0, dice_coef = 0, dice_val = 0;   // train, loss kind 4: per-image partial rows, (c0, c1) and Dice values
     // EvalNet
     size_t cat = 0, dcat = 0;      // concatenated pooled tower outputs [B,H/2,W/2,2F] and their gradient
     size_t onehot = 0;             // b_onehot: input B as fp16 one-hot [B,H,W,pad8(cb)]

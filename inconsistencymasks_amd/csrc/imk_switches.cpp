@@ -30,6 +30,7 @@ const ImkSwitches &imk_switches() {
         v.wgrad_nfo2 = on_unless_zero("IMK_WGRAD_NFO2");
         v.student_fused = on_unless_zero("IMK_STUDENT_FUSED");
         v.consistency_fused = on_unless_zero("IMK_CONSISTENCY_FUSED");
+        v.dice_fused = on_unless_zero("IMK_DICE_FUSED");
         v.select_shared = on_unless_zero("IMK_SELECT_SHARED");
         const int n = int_or("IMK_SIDE_STREAMS", 1);
         v.side_streams = n < 0 ? 0 : (n > imk_unet_plan::MAX_SIDE ? imk_unet_plan::MAX_SIDE : n);

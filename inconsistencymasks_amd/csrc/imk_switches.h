@@ -18,6 +18,7 @@ struct ImkSwitches {
     bool wgrad_nfo2;          // IMK_WGRAD_NFO2=0: no two-output-tile form of the GEMM-class 3x3 weight gradient
     bool student_fused;       // IMK_STUDENT_FUSED=0: imk_unet_forward_student takes forward -> label -> imk_augment for every shape
     bool consistency_fused;   // IMK_CONSISTENCY_FUSED=0: imk_unet_consistency_fwd_bwd takes head_kernel x 2 -> consistency_dlogit_kernel -> the head's dgrad for every shape
+    bool dice_fused;          // IMK_DICE_FUSED=0: loss kind 4 takes dice_dlogit_kernel -> the head's dgrad for every shape (no head_mse_fused_kernel variant)
     bool select_shared;       // IMK_SELECT_SHARED=0: imk_evalnet_forward_select scores through imk_evalnet_forward on the repeated images
     int side_streams;         // IMK_SIDE_STREAMS: side streams of a training step's weight gradients, 0 ... MAX_SIDE (default 1)
 };

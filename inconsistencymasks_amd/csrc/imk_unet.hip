@@ -112,6 +112,9 @@ Ws make_ws(const imk_unet_plan *p, int B, int mode) {
         w.dlogit = take(px * imk_pad8(p->cfg.n_out) * 2);
         w.loss_partial = take((size_t)imk_loss_blocks((long long)px) * sizeof(float));
         w.probs = take(px * p->cfg.n_out * sizeof(float));
+        w.dice_partial = take((size_t)B * imk_dice_rows(B, p->cfg.h * p->cfg.w) * 3 * sizeof(float));
+        w.dice_coef = take((size_t)B * 2 * sizeof(float));
+        w.dice_val = take((size_t)B * sizeof(double));
     }
     w.total = off;
     return w;
@@ -777,9 +780,10 @@ extern "C" int imk_unet_fwd_bwd(const imk_unet_plan *plan, float *params, void *
                                 const uint8_t *y, int batch, int loss_kind, float *grads, float *stats, void *workspace,
                                 int64_t workspace_bytes, void *stream_) {
     IMK_CHECK_ARG(plan && params && packed && state && x && y && grads && stats && workspace && batch > 0);
-    IMK_CHECK_ARG(loss_kind >= 0 && loss_kind <= 3);
-    IMK_CHECK_ARG((loss_kind != 1) == (plan->cfg.act_out == 0));  // mse / rmse <-> sigmoid head, cce <-> softmax head
-    const int y255 = loss_kind >= 2;                              // kinds 2, 3: continuous targets y / 255.0f
+    IMK_CHECK_ARG(loss_kind >= 0 && loss_kind <= 4);
+    IMK_CHECK_ARG((loss_kind != 1) == (plan->cfg.act_out == 0));  // mse / rmse / Dice <-> sigmoid head, cce <-> softmax head
+    const int y255 = loss_kind == 2 || loss_kind == 3;            // kinds 2, 3: continuous targets y / 255.0f
+    const bool dice = loss_kind == 4;                             // the per-image Dice loss: sums -> coefficients -> gradient (imk_dice.hip)
     const int fin_kind = loss_kind == 1 ? 1 : 0;                  // the loss finalize's denominator: every element, or every pixel
     hipStream_t stream = (hipStream_t)stream_;
     Ctx c{plan, make_ws(plan, batch, 1), (uint8_t *)workspace, params, (const uint8_t *)packed, batch, true, stream};
@@ -804,8 +808,18 @@ extern "C" int imk_unet_fwd_bwd(const imk_unet_plan *plan, float *params, void *
     const bool head_one_pass = cf.act_out == 1 &&
                                imk_head_cce_fused_ok(imk_pad8(ol.cin), ol.cout, n_pix, c.ws.L[obn].n_bwd_rows);
     // sigmoid heads with 1 / 3 maps on <= 16 channels (ISIC, HeLa): the same in one pass (head_mse_fused_kernel, round 4)
-    const bool head_mse_pass = cf.act_out == 0 && imk_head_mse_fused_ok(imk_pad8(ol.cin), ol.cout, n_pix, c.ws.L[obn].n_bwd_rows);
-    if (!head_one_pass && !head_mse_pass)
+    const bool head_mse_pass = cf.act_out == 0 && imk_head_mse_fused_ok(imk_pad8(ol.cin), ol.cout, n_pix, c.ws.L[obn].n_bwd_rows) &&
+                               (!dice || imk_switches().dice_fused);
+    float *dice_coef = reinterpret_cast<float *>(c.base + c.ws.dice_coef);
+    if (dice) {
+        float *rows = reinterpret_cast<float *>(c.base + c.ws.dice_partial);
+        OK(imk_launch_dice_sums(c.act(t.d_c1[3]), c.bn_scale(obn), c.bn_shift(obn), params + ol.off_w, params + ol.off_b, ol.cin,
+                                imk_pad8(ol.cin), ol.cout, batch, cf.h * cf.w, y, sv.ctl, stats, rows, stream));
+        OK(imk_launch_dice_coef(rows, batch, cf.h * cf.w, dice_coef, reinterpret_cast<double *>(c.base + c.ws.dice_val), stats, stream));
+        if (!head_mse_pass)
+            OK(imk_launch_dice_dlogit(c.act(t.d_c1[3]), c.bn_scale(obn), c.bn_shift(obn), params + ol.off_w, params + ol.off_b, ol.cin,
+                                      imk_pad8(ol.cin), ol.cout, n_pix, cf.h * cf.w, y, sv.ctl, dice_coef, dlogit, stream));
+    } else if (!head_one_pass && !head_mse_pass)
         OK(imk_launch_head_loss(c.act(t.d_c1[3]), c.bn_scale(obn), c.bn_shift(obn), params + ol.off_w, params + ol.off_b, ol.cin,
                                 imk_pad8(ol.cin), ol.cout, cf.act_out, n_pix, y, sv.ctl, stats, dlogit, loss_partial, stream, y255));
 
@@ -817,7 +831,7 @@ extern "C" int imk_unet_fwd_bwd(const imk_unet_plan *plan, float *params, void *
     const bool side_on = !plan->dbg_single_stream && n_side > 0 && ensure_side_streams(plan, n_side);
     Bwd b{c, grads, sv.ctl, stats + 1, side_on ? n_side : 0};
     ImkStopRingScope stop_ring(plan, stream, b.n_side);      // from here on: the backward pass's launches carry their own events
-    bool loss_done = false;
+    bool loss_done = dice;                  // kind 4: dice_coef_kernel wrote stats[0]
     auto loss_on_side = [&]() -> int {      // once, as soon as a fork exists (every fork event is younger than the head's kernel)
         if (loss_done || b.n_side <= 0 || b.n_fork <= 0 || loss_kind == 3) return IMK_OK;      // kind 3: on `stream`, in front of its scaling launch
         loss_done = true;
@@ -830,7 +844,8 @@ extern "C" int imk_unet_fwd_bwd(const imk_unet_plan *plan, float *params, void *
         float *wgp = reinterpret_cast<float *>(c.base + c.ws.L[t.out].wg_partial);
         OK(imk_launch_head_mse_fused(c.act(t.d_c1[3]), c.bn_scale(obn), c.bn_shift(obn), params + ol.off_w, params + ol.off_b,
                                      ol.cin, imk_pad8(ol.cin), ol.cout, n_pix, y, sv.ctl, stats, c.dy(obn), loss_partial,
-                                     reinterpret_cast<float *>(c.base + c.ws.L[obn].bwd_partial), wgp, stream, y255));
+                                     reinterpret_cast<float *>(c.base + c.ws.L[obn].bwd_partial), wgp, stream, y255,
+                                     dice ? dice_coef : nullptr, cf.h * cf.w));
         head_rows = rows;
         head_job = HeadWgJob{wgp, rows};
     } else if (head_one_pass) {

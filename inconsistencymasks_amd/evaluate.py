@@ -71,3 +71,21 @@ def soft_sums(probs, gt, mode):
           "imk_eval_soft_sums")
     res = out[:3 * K].cpu().numpy()
     return res.reshape(3, K) if mode == 0 else float(res[0])
+
+
+def dice_sums(probs, gt):
+    """The per-image sums of the reference's dice_loss (functions.py:162-184) on the device (imk_eval_dice_sums), deterministic:
+    probs [B,H,W,K] f32 cuda, gt [B,H,W,K] u8 cuda targets -> float64 numpy [B,3] = (sum t p, sum t, sum p).  An image's row does not
+    depend on the batch it is in."""
+    probs, gt = probs.contiguous(), gt.contiguous()
+    assert probs.is_cuda and probs.dtype == torch.float32 and gt.dtype == torch.uint8 and probs.dim() == 4 and gt.shape == probs.shape
+    B, H, W, K = probs.shape
+    out = torch.empty((B, 3), dtype=torch.float64, device=probs.device)
+    check(lib.imk_eval_dice_sums(probs.data_ptr(), gt.data_ptr(), B, H, W, K, out.data_ptr(), _stream()), "imk_eval_dice_sums")
+    return out.cpu().numpy()
+
+
+def dice_from_sums(sums, smooth=1):
+    """dice_b = (2 I_b + smooth) / (U_b + smooth) per row of dice_sums' result, in float64"""
+    sums = np.asarray(sums, dtype=np.float64)
+    return (2.0 * sums[:, 0] + smooth) / (sums[:, 1] + sums[:, 2] + smooth)

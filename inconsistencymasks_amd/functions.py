@@ -683,8 +683,9 @@ def create_augment_images_and_masks_hela(main_input_path, main_output_path, num_
 # metrics (functions.py:162-184, 1767-1861)
 # ---------------------------------------------------------------------------------------------------
 def dice_loss(y_true, y_pred, smooth=1):
-    """functions.py:162-184 on arrays [B,H,W,K] (the `custom_objects` entry of the scripts' load_model calls; no shipped
-    script trains with it)."""
+    """functions.py:162-184 on arrays [B,H,W,K] (the `custom_objects` entry of the scripts' load_model calls).  Passed to
+    train_ISIC_2018 / train_hela as `loss_func` (the function, or the string 'dice_loss') it selects the fused training step's loss
+    kind 4, the same rule with smooth = 1 on the sigmoid head."""
     y_true = np.asarray(y_true, dtype=np.float32)
     y_pred = np.asarray(y_pred, dtype=np.float32)
     inter = (y_true * y_pred).sum(axis=(1, 2, 3))
@@ -736,9 +737,29 @@ class ignore_im_dice_loss_multiclass:
 _UNTRAINABLE_LOSSES = (ignore_im_categorical_crossentropy, ignore_im_dice_loss_multiclass)
 
 
+def _is_dice_loss(loss_func):
+    return loss_func is dice_loss or (isinstance(loss_func, str) and loss_func == "dice_loss")
+
+
+def _sigmoid_loss_kind(loss_func, who):
+    """loss kind of imk_unet_fwd_bwd for the two sigmoid-head trainers: 'mse' -> 0, dice_loss (or 'dice_loss') -> 4"""
+    if isinstance(loss_func, str) and loss_func == "mse":
+        return 0
+    if _is_dice_loss(loss_func):
+        return 4
+    _reject_untrainable(loss_func, who)
+    raise NotImplementedError(f"{who}: sigmoid heads train with 'mse' or dice_loss, got {loss_func!r}")
+
+
 def _reject_untrainable(loss_func, who):
-    """the losses no reference script trains with have no fused kernel: say so instead of silently training with another loss"""
-    if isinstance(loss_func, _UNTRAINABLE_LOSSES) or loss_func in _UNTRAINABLE_LOSSES or loss_func is dice_loss:
+    """the losses no reference script trains with have no fused kernel: say so instead of silently training with another loss
+    (dice_loss trains the sigmoid heads of train_ISIC_2018 / train_hela, which do not come here with it)"""
+    if _is_dice_loss(loss_func):
+        if who == "train_multiclass":
+            raise NotImplementedError(f"{who}: the reference's dice_loss is the binary form (one Dice over an image's sigmoid maps); "
+                                      "there is no fused training kernel for it on a softmax head -- train_ISIC_2018 / train_hela take it")
+        raise NotImplementedError(f"{who}: no fused training kernel for dice_loss here; train_ISIC_2018 / train_hela take it")
+    if isinstance(loss_func, _UNTRAINABLE_LOSSES) or loss_func in _UNTRAINABLE_LOSSES:
         name = getattr(loss_func, "__name__", type(loss_func).__name__)
         raise NotImplementedError(f"{who}: no fused training kernel for {name} (imported by some reference scripts, passed by none); "
                                   "the scripts train with 'mse' / CategoricalCrossentropy()")
@@ -1136,9 +1157,8 @@ def benchmark_ISIC2018(model, images_dir, masks_dir, pred_path, h, w, c, batch_s
 def train_ISIC_2018(train_images_dir, val_images_dir, val_masks_dir, test_images_dir, test_masks_dir,
                     unlabeled_images_dir, unlabeled_masks_dir, modelname, filepath_h5, model, loss_func,
                     steps_per_epoch, h, w, c, val_pred_dir, test_pred_dir, unlabeled_pred_dir, print_results=False):
-    """functions.py:189-228.  loss_func must be 'mse' (what every ISIC script passes)."""
-    if loss_func != "mse":
-        raise NotImplementedError("the ISIC scripts train with 'mse'")
+    """functions.py:189-228.  loss_func: 'mse' (what every ISIC script passes) or dice_loss (loss kind 4)."""
+    kind = _sigmoid_loss_kind(loss_func, "train_ISIC_2018")
     files = _train_shard(glob.glob(os.path.join(train_images_dir, "*.png")))
     loader = _EpochLoader(files, lambda p: parse_image_ISIC_2018(p, c), BATCH_SIZE, SEED, ("isic", c))
     best = {"iou": -1.0}
@@ -1150,7 +1170,7 @@ def train_ISIC_2018(train_images_dir, val_images_dir, val_masks_dir, test_images
             if _rank_world()[0] == 0:
                 save_model(model, filepath_h5)
 
-    fit(model, loader, steps_per_epoch, NUM_EPOCHS, 0, on_epoch_end)
+    fit(model, loader, steps_per_epoch, NUM_EPOCHS, kind, on_epoch_end)
     d = _dist()
     if d:
         d.barrier()
@@ -1818,9 +1838,8 @@ def benchmark_hela(model, gt_main_dir, pred_dir, h, w, c, threshold=0.5, batch_s
 
 def train_hela(train_images_dir, val_images_dir, val_gt_dir, test_gt_dir, unlabeled_gt_dir, modelname, filepath_h5, model,
                loss_func, steps_per_epoch, h, w, c, val_pred_dir, test_pred_dir, unlabeled_pred_dir):
-    """functions.py:232-269: 'mse' on (alive, dead, 3 x position) targets, best epoch by val_loss (min)."""
-    if loss_func != "mse":
-        raise NotImplementedError("the HeLa scripts train with 'mse'")
+    """functions.py:232-269: 'mse' or dice_loss (loss kind 4) on (alive, dead, 3 x position) targets, best epoch by val_loss (min)."""
+    kind = _sigmoid_loss_kind(loss_func, "train_hela")
     files = _train_shard(glob.glob(os.path.join(train_images_dir, "*.png")))
     loader = _EpochLoader(files, lambda p: parse_image_hela(p, c), BATCH_SIZE, SEED, ("hela", c))
     val_files = sorted(glob.glob(os.path.join(val_images_dir, "*.png")))
@@ -1836,18 +1855,23 @@ def train_hela(train_images_dir, val_images_dir, val_gt_dir, test_gt_dir, unlabe
                 _VAL_CACHE[key] = _uploaded(torch.from_numpy(np.stack([it[0] for it in items], 0)).cuda(),
                                             torch.from_numpy(np.stack([it[1] for it in items], 0)).cuda())
             xs, ys = _used_here(_VAL_CACHE[key])
-        sq, n = 0.0, 0
-        for i in range(0, len(val_files), BATCH_SIZE):
-            y = ys[i:i + BATCH_SIZE]
-            sq += _ev.soft_sums(model.predict_device(xs[i:i + BATCH_SIZE]), y, 1)
-            n += y.numel()
-        val_loss = sq / max(n, 1)
+        if kind == 4:       # the sample-weighted mean of the batches' Dice losses = 1 - the mean of dice_b over all validation images
+            dices = [_ev.dice_from_sums(_ev.dice_sums(model.predict_device(xs[i:i + BATCH_SIZE]), ys[i:i + BATCH_SIZE]))
+                     for i in range(0, len(val_files), BATCH_SIZE)]
+            val_loss = 1.0 - float(np.mean(np.concatenate(dices))) if dices else 0.0
+        else:
+            sq, n = 0.0, 0
+            for i in range(0, len(val_files), BATCH_SIZE):
+                y = ys[i:i + BATCH_SIZE]
+                sq += _ev.soft_sums(model.predict_device(xs[i:i + BATCH_SIZE]), y, 1)
+                n += y.numel()
+            val_loss = sq / max(n, 1)
         if val_loss < best["loss"]:
             best["loss"] = val_loss
             if _rank_world()[0] == 0:
                 save_model(model, filepath_h5)
 
-    fit(model, loader, steps_per_epoch, NUM_EPOCHS, 0, on_epoch_end)
+    fit(model, loader, steps_per_epoch, NUM_EPOCHS, kind, on_epoch_end)
     d = _dist()
     if d:
         d.barrier()
