@@ -97,9 +97,36 @@ IMK_API int imk_im_multiclass(const float *probs, int n_models, int batch, int h
                       uint8_t *img_out, uint8_t *final_out, uint8_t *im_out,
                       int64_t *im_size, uint8_t *presence, void *stream);
 
+/* The IM over per-image sub-ensembles of a model pool: the rule the EvalNet training-data writers of the IM++ family apply to
+ * `random.sample(models, n)` per image (create_training_data_evalnet_im_binary, functions.py:3621-3640;
+ * create_training_data_evalnet_miou_im_multiclass, :3826; create_training_data_evalnet_miou_im_hela, :3931-3953).  The arguments
+ * of imk_im_binary / imk_im_multiclass, whose stack holds the whole pool (n_models <= 16), and
+ *   members    [B] uint32: bit n set = model n of the pool votes for image b; bits at and above n_models are ignored.
+ * With cnt_b the number of members of image b:
+ *   binary: s = the members' votes; masks_out = 255 where s == cnt_b; IM where s != 0 and s != cnt_b; sizes before blocking;
+ *   multi-class: final_out = the label where all members' arg-maxes agree, else 0 (the reference anchors on the first sampled
+ *     model; agreement is symmetric, so the sampling order does not matter); presence rows of non-members are 0.
+ *   cnt_b == 0: labels 0, IM 0, sizes 0, the image copied.
+ * Non-members' probabilities are not read.  With every bit set the outputs equal imk_im_binary / imk_im_multiclass bit for bit.
+ * batch <= 65535.                                                                                             */
+IMK_API int imk_im_binary_members(const float *preds, const uint32_t *members, int n_models, int batch, int h, int w, int kb,
+                  float thr, int cmp_ge,
+                  const uint8_t *img, int c, int block_in, int block_out,
+                  uint8_t *img_out, uint8_t *masks_out, uint8_t *im_out,
+                  int64_t *im_size, int64_t *pred_size, void *stream);
+IMK_API int imk_im_multiclass_members(const float *probs, const uint32_t *members, int n_models, int batch, int h, int w, int k,
+                      const uint8_t *img, int c, int block_in, int block_out,
+                      uint8_t *img_out, uint8_t *final_out, uint8_t *im_out,
+                      int64_t *im_size, uint8_t *presence, void *stream);
+
 /* k x k all-ones erosion (op = 0) / dilation (op = 1) of [B,H,W] uint8 masks, out-of-image taps ignored.
  * Replaces cv2.erode / cv2.dilate at functions.py:2858-2864 (dead in every shipped config: EK = DK = 0). */
 IMK_API int imk_morph(const uint8_t *src, uint8_t *dst, int batch, int h, int w, int ksize, int op, void *stream);
+
+/* imk_morph with one window per image: ksizes [B] int32 (device), image b gets a ksizes[b] x ksizes[b] window and is bit-identical
+ * to imk_morph(ksize = ksizes[b]) on that image; 0 (or less) copies the image, sizes above 31 count as 31.  One launch for the
+ * per-image random erosion / dilation of the writers above (functions.py:3626-3634, 3946-3954).  batch <= 65535.            */
+IMK_API int imk_morph_var(const uint8_t *src, uint8_t *dst, int batch, int h, int w, const int32_t *ksizes, int op, void *stream);
 
 /* image[im>0] = 0 (all C channels) and mask[im>0] = 0 for n_masks [B,H,W] masks packed as [B,n_masks,H,W]:
  * the blocking step of functions.py:2867-2874 when it has to run AFTER morphology changed the IM.
@@ -213,6 +240,26 @@ IMK_API int64_t imk_unet_forward_im_workspace_bytes(const imk_unet_plan *plan, i
 IMK_API int imk_unet_forward_im(const imk_unet_plan *plan, int n_models,
                         const float *const *params, const void *const *packed,
                         const uint8_t *x, int batch, float thr, int cmp_ge,
+                        const uint8_t *img, int block_in, int block_out,
+                        uint8_t *img_out, uint8_t *masks_out, uint8_t *im_out,
+                        int64_t *im_size, int64_t *pred_size, uint8_t *presence,
+                        void *workspace, int64_t workspace_bytes, void *stream);
+
+/* imk_unet_forward_im over per-image sub-ensembles of a pool of n_models <= 16 models: image b is judged by the models whose bit
+ * is set in members_host[b] (a HOST array [B], like `params` and `packed`; bits at and above n_models are ignored; the call copies
+ * it into the workspace as kernel arguments: the array is the caller's again when the call returns, and nothing waits for `stream`).  Each model runs once, on the images that use it (a model nobody uses does not run), and one head + IM
+ * kernel reads, for every image, its members' last decoder activations.  Outputs as imk_unet_forward_im, with the rule and the
+ * `presence` layout [n_models,B,K] of imk_im_binary_members / imk_im_multiclass_members.
+ * Bit-identical to imk_unet_forward per pool model + imk_im_*_members; for images that share a member set, bit-identical to
+ * imk_unet_forward_im on that set (the forward does not depend on the batch an image sits in).
+ * workspace: imk_unet_forward_im_members_workspace_bytes(plan, n_models, B, k), 1 <= k <= 3 concurrent streams as for
+ * imk_unet_forward_im; the size for k = 1 is the least the call accepts.  Shapes the fused kernel does not cover (those of
+ * imk_unet_forward_im), an image with more than 8 members and plans with the materialize debug switch take the unfused route
+ * inside the same workspace: every used model on the whole batch -> fp32 stack -> imk_im_*_members.  batch <= 65535. */
+IMK_API int64_t imk_unet_forward_im_members_workspace_bytes(const imk_unet_plan *plan, int n_models, int batch, int n_streams);
+IMK_API int imk_unet_forward_im_members(const imk_unet_plan *plan, int n_models,
+                        const float *const *params, const void *const *packed,
+                        const uint8_t *x, int batch, const uint32_t *members_host, float thr, int cmp_ge,
                         const uint8_t *img, int block_in, int block_out,
                         uint8_t *img_out, uint8_t *masks_out, uint8_t *im_out,
                         int64_t *im_size, int64_t *pred_size, uint8_t *presence,

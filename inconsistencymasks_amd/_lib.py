@@ -49,6 +49,13 @@ SIGNATURES = {
     "imk_im_multiclass": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int,
                                   c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_void_p, c_void_p]),
+    "imk_im_binary_members": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_int,
+                                      c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                      c_void_p, c_void_p, c_void_p]),
+    "imk_im_multiclass_members": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                          c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p]),
+    "imk_morph_var": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
     "imk_morph": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "imk_block_apply": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "imk_unet_plan_create": (c_int, [ctypes.POINTER(UnetCfg), ctypes.POINTER(c_void_p)]),
@@ -68,6 +75,11 @@ SIGNATURES = {
                                     c_void_p, c_int, c_float, c_int, c_void_p, c_int, c_int,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                     c_void_p, c_int64, c_void_p]),
+    "imk_unet_forward_im_members_workspace_bytes": (c_int64, [c_void_p, c_int, c_int, c_int]),
+    "imk_unet_forward_im_members": (c_int, [c_void_p, c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),
+                                            c_void_p, c_int, ctypes.POINTER(ctypes.c_uint32), c_float, c_int, c_void_p, c_int, c_int,
+                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            c_void_p, c_int64, c_void_p]),
     "imk_vote_binary": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_void_p]),
     "imk_vote_multiclass": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "imk_unet_forward_vote": (c_int, [c_void_p, c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p),

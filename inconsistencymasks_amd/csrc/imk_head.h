@@ -244,6 +244,32 @@ struct ImkHeadImArgs {
 bool imk_head_im_supported(const ImkHeadImArgs &a);
 int imk_launch_head_im(const ImkHeadImArgs &a, hipStream_t stream);
 
+// ---- fused head + inconsistency mask over per-image members of a model pool (imk_members.hip) --------------------------------
+#define IMK_MEMBERS_MAX_POOL 16
+struct ImkHeadImMembersArgs {
+    const f16 *z[IMK_MEMBERS_MAX_POOL];          // model n's last decoder conv output [count_n,H,W,cs]: the images that use it
+    const float *sc[IMK_MEMBERS_MAX_POOL], *sh[IMK_MEMBERS_MAX_POOL];       // its folded BatchNorm
+    const float *w[IMK_MEMBERS_MAX_POOL], *bias[IMK_MEMBERS_MAX_POOL];      // the head's fp32 kernel [cin][K] / bias [K]
+    const uint32_t *members;                     // device [B]: bit n = model n votes for image b
+    const int *row;                              // device [n_models][B]: image b's position in model n's batch (members only)
+    int n_models, cin, cs, K, softmax;
+    int batch, hw;
+    float thr;
+    int cmp_ge;
+    const uint8_t *img;
+    int c, block_in, block_out;
+    uint8_t *img_out, *masks_out, *im_out;
+    int64_t *im_size, *pred_size;
+    uint8_t *presence;
+};
+// The shapes of imk_head_im_supported, a pool of at most 16 models and at most 8 members per image.
+bool imk_head_im_members_supported(const ImkHeadImMembersArgs &a, int max_members);
+int imk_launch_head_im_members(const ImkHeadImMembersArgs &a, int max_members, hipStream_t stream);
+// the host's member words into a device array [B], as kernel arguments (nothing waits for the stream)
+void imk_launch_members_upload(const uint32_t *members_host, int batch, uint32_t *dst, hipStream_t stream);
+// list [n_models][B] int64 (the images of model n, in order) and row [n_models][B] from the member words; one launch
+void imk_launch_members_lists(const uint32_t *members, int n_models, int batch, int64_t *list, int *row, hipStream_t stream);
+
 // ---- fused head + standard-deviation map of the depth-map IM (imk_depth.hip) ------------------------------------------------
 struct ImkDepthHeadArgs {
     const f16 *z[IMK_HEAD_IM_MAX_MODELS];        // last decoder block's conv output [B,H,W,cs] of every model

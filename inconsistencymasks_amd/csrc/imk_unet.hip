@@ -419,6 +419,132 @@ extern "C" int imk_unet_forward_im(const imk_unet_plan *plan, int n_models, cons
                              img_out, masks_out, im_out, im_size, presence, stream_);
 }
 
+// Ensemble inference + IM over per-image members of a model pool.  Workspace: [member words u32 [B] | image lists int64 [N][B] |
+// rows int32 [N][B] | N head slabs | per concurrent stream: a compacted input batch and an activation workspace].  Fused: model n
+// runs on the images that use it (gathered by its list) and leaves their last decoder activations in its slab; one head + IM kernel
+// (imk_members.hip) reads, for image b, the slabs of b's members at row[n][b].  Unfused (shapes the kernel does not cover, more than
+// 8 members in some image, imk_debug_materialize(1)): every model that anybody uses runs on the whole batch into the fp32 stack
+// [N,B,H,W,K] at the start of the slabs, then imk_im_*_members.
+struct MembersLayout {
+    size_t list, row, slabs, slab, xbuf, per_stream, fixed;
+};
+static MembersLayout members_layout(const imk_unet_plan *plan, int n_models, int batch) {
+    const imk_unet_cfg &cf = plan->cfg;
+    MembersLayout l;
+    l.list = up((size_t)batch * sizeof(uint32_t));
+    l.row = l.list + up((size_t)n_models * batch * sizeof(int64_t));
+    l.slabs = l.row + up((size_t)n_models * batch * sizeof(int));
+    l.slab = head_slab_bytes(plan, batch, true);
+    l.xbuf = up((size_t)batch * cf.h * cf.w * cf.c_in);
+    l.per_stream = l.xbuf + make_ws(plan, batch, 0).total;
+    l.fixed = l.slabs + l.slab * n_models;
+    return l;
+}
+
+extern "C" int64_t imk_unet_forward_im_members_workspace_bytes(const imk_unet_plan *plan, int n_models, int batch, int n_streams) {
+    if (!plan || plan->net != 0 || n_models <= 0 || n_models > IMK_MEMBERS_MAX_POOL || batch <= 0 || n_streams <= 0) return IMK_EINVAL;
+    const MembersLayout l = members_layout(plan, n_models, batch);
+    return (int64_t)(l.fixed + l.per_stream * n_streams);
+}
+
+extern "C" int imk_unet_forward_im_members(const imk_unet_plan *plan, int n_models, const float *const *params,
+                                           const void *const *packed, const uint8_t *x, int batch, const uint32_t *members_host,
+                                           float thr, int cmp_ge, const uint8_t *img, int block_in, int block_out, uint8_t *img_out,
+                                           uint8_t *masks_out, uint8_t *im_out, int64_t *im_size, int64_t *pred_size,
+                                           uint8_t *presence, void *workspace, int64_t workspace_bytes, void *stream_) {
+    IMK_CHECK_ARG(plan && plan->net == 0 && params && packed && x && members_host && workspace && batch > 0 && batch <= 65535);
+    IMK_CHECK_ARG(n_models > 0 && n_models <= IMK_MEMBERS_MAX_POOL);
+    IMK_CHECK_ARG(masks_out && im_out && im_size && (plan->cfg.act_out != 0 || pred_size) && (!img || img_out));
+    const imk_unet_cfg &cf = plan->cfg;
+    const MembersLayout lay = members_layout(plan, n_models, batch);
+    if ((int64_t)(lay.fixed + lay.per_stream) > workspace_bytes) return IMK_EWORKSPACE;
+    // each model's images, counted on the host
+    const uint32_t pool = (n_models >= 32) ? 0xffffffffu : ((1u << n_models) - 1u);
+    int count[IMK_MEMBERS_MAX_POOL] = {0}, max_members = 0;
+    for (int b = 0; b < batch; ++b) {
+        const uint32_t word = members_host[b] & pool;
+        max_members = std::max(max_members, __builtin_popcount(word));
+        for (int n = 0; n < n_models; ++n) count[n] += (word >> n) & 1u;
+    }
+    uint8_t *base = (uint8_t *)workspace;
+    uint32_t *d_members = (uint32_t *)base;
+    int64_t *d_list = (int64_t *)(base + lay.list);
+    int *d_row = (int *)(base + lay.row);
+    hipStream_t main_stream = (hipStream_t)stream_;
+    const Topo topo = make_topo(plan);
+    const ImkLayer &o = plan->layers[topo.out];
+    ImkHeadImMembersArgs ha{};
+    ha.members = d_members; ha.row = d_row;
+    ha.n_models = n_models; ha.cin = cf.ch[0]; ha.cs = imk_pad8(cf.ch[0]); ha.K = cf.n_out; ha.softmax = cf.act_out;
+    ha.batch = batch; ha.hw = cf.h * cf.w; ha.thr = thr; ha.cmp_ge = cmp_ge; ha.img = img; ha.c = cf.c_in;
+    ha.block_in = block_in; ha.block_out = block_out; ha.img_out = img_out; ha.masks_out = masks_out; ha.im_out = im_out;
+    ha.im_size = im_size; ha.pred_size = pred_size; ha.presence = presence;
+    const bool fused = !plan->dbg_materialize && imk_head_im_members_supported(ha, max_members);
+    // a model's forward at its own batch: the activation workspace of a smaller batch fits the full batch's
+    Ws ws_of[IMK_MEMBERS_MAX_POOL];
+    const Ws ws_full = make_ws(plan, batch, 0);
+    for (int n = 0; n < n_models; ++n) {
+        if (!count[n]) continue;
+        ws_of[n] = (fused && count[n] < batch) ? make_ws(plan, count[n], 0) : ws_full;
+        if (ws_of[n].total > ws_full.total) return IMK_EWORKSPACE;
+    }
+    imk_launch_members_upload(members_host, batch, d_members, main_stream);
+    IMK_LAUNCH_CHECK();
+    if (fused) {
+        imk_launch_members_lists(d_members, n_models, batch, d_list, d_row, main_stream);
+        IMK_LAUNCH_CHECK();
+    }
+    const int max_streams = 1 + imk_unet_plan::MAX_SIDE;
+    int n_used = 0;
+    for (int n = 0; n < n_models; ++n) n_used += count[n] > 0;
+    int n_slabs = (int)(((size_t)workspace_bytes - lay.fixed) / lay.per_stream);
+    if (n_slabs > n_used) n_slabs = n_used;
+    if (n_slabs > max_streams) n_slabs = max_streams;
+    if (n_slabs > 1 && (plan->dbg_single_stream || !ensure_side_streams(plan, n_slabs - 1))) n_slabs = 1;
+    if (n_slabs > 1) {
+        IMK_HIP(hipEventRecord(plan->ev_fork[0], main_stream));
+        for (int s = 1; s < n_slabs; ++s) IMK_HIP(hipStreamWaitEvent(plan->side[s - 1], plan->ev_fork[0], 0));
+    }
+    const size_t probs_exact = (size_t)batch * cf.h * cf.w * cf.n_out * sizeof(float);
+    const int64_t row_img = (int64_t)cf.h * cf.w * cf.c_in;
+    int used = 0;
+    for (int n = 0; n < n_models; ++n) {
+        if (!count[n]) continue;        // nobody uses this model
+        const int sl = used++ % n_slabs;
+        hipStream_t st = sl == 0 ? main_stream : plan->side[sl - 1];
+        uint8_t *region = base + lay.fixed + lay.per_stream * sl;
+        const int nb = fused ? count[n] : batch;
+        const uint8_t *xin = x;
+        if (nb < batch) {
+            int rc = imk_gather_pairs(x, row_img, nullptr, 0, 0, 0, nullptr, d_list + (size_t)n * batch, nb, region, nullptr, st);
+            if (rc) return rc;
+            xin = region;
+        }
+        Ctx c{plan, ws_of[n], region + lay.xbuf, params[n], (const uint8_t *)packed[n], nb, false, st};
+        c.x_in[0] = xin;
+        if (fused) {    // the last decoder activation goes to the model's head slab; no head launch
+            c.ovr_conv = topo.d_c1[3];
+            c.ovr_out = reinterpret_cast<f16 *>(base + lay.slabs + lay.slab * n);
+            ha.z[n] = c.ovr_out;
+            ha.sc[n] = c.bn_scale(topo.d_bnb[3]); ha.sh[n] = c.bn_shift(topo.d_bnb[3]);
+            ha.w[n] = params[n] + o.off_w; ha.bias[n] = params[n] + o.off_b;
+        }
+        int rc = run_forward(c, topo, fused ? nullptr : (float *)(base + lay.slabs + probs_exact * n), nullptr);
+        if (rc) return rc;
+    }
+    for (int s = 1; s < n_slabs; ++s) {
+        IMK_HIP(hipEventRecord(plan->ev_join[s - 1], plan->side[s - 1]));
+        IMK_HIP(hipStreamWaitEvent(main_stream, plan->ev_join[s - 1], 0));
+    }
+    if (fused) return imk_launch_head_im_members(ha, max_members, main_stream);
+    const float *stack = (const float *)(base + lay.slabs);
+    if (cf.act_out == 0)
+        return imk_im_binary_members(stack, d_members, n_models, batch, cf.h, cf.w, cf.n_out, thr, cmp_ge, img, cf.c_in, block_in,
+                                     block_out, img_out, masks_out, im_out, im_size, pred_size, stream_);
+    return imk_im_multiclass_members(stack, d_members, n_models, batch, cf.h, cf.w, cf.n_out, img, cf.c_in, block_in, block_out,
+                                     img_out, masks_out, im_out, im_size, presence, stream_);
+}
+
 // Ensemble inference + the depth-map family's standard-deviation IM.  Workspace: [the std map, B*H*W fp32 | imk_unet_forward_im's
 // workspace]: the model loop of imk_unet_forward_im, then the fused head + std kernel on the activation slabs (imk_depth.hip), or --
 // for the shapes it does not cover -- imk_im_depth's first launch on the probability stack; the thresholds and the mask either way.

@@ -51,6 +51,67 @@ def _groups(plan):
     return g
 
 
+# IMK_TRAINDATA_POOLED, read once: 1 (default) = a loop's images go through ONE model pool in file order (PoolIM: per-image member
+# sets, one ensemble call per INFER_BATCH chunk, one imk_morph_var per operation); 0 = the images are grouped by sub-ensemble and
+# every group runs its own EnsembleIM (also the route of a pool of more than 16 models, which a member word does not hold).  Both
+# routes write the same bytes (tests/test_gpu_traindata_members.py); DESIGN.md has the measurement that chose the default.
+POOLED = os.environ.get("IMK_TRAINDATA_POOLED", "1") != "0"
+
+
+def _var_morph(im, plan, idx):
+    """_random_morph in two launches: every image's own window, 0 = untouched"""
+    for op, col in (("erode", 1), ("dilate", 2)):
+        ks = [plan[i][col] for i in idx]
+        if any(ks):
+            im = _im.morph_var(im, ks, op)
+    return im
+
+
+def _chunks(plan, batch, pooled):
+    """the (subset or None, image indices) chunks of one loop: grouped by sub-ensemble, or the file list in order"""
+    if pooled:
+        n = len(plan)
+        return [(None, list(range(s, min(s + batch, n)))) for s in range(0, n, batch)]
+    return [(subset, idx_all[s:s + batch]) for subset, idx_all in _groups(plan).items() for s in range(0, len(idx_all), batch)]
+
+
+def _draw_aug(plan, batch, draw_kw):
+    """the augmentation draws of one loop, per image, made in the grouped route's order (group by group, chunk by chunk, the
+    augmented images of a chunk in order) whichever route runs: the random streams do not depend on the route"""
+    prm = {}
+    for _, idx in _chunks(plan, batch, False):
+        sel = [i for i in idx if plan[i][3]]
+        if sel:
+            for i, q in zip(sel, draw_params(len(sel), **draw_kw)):
+                prm[i] = q
+    return prm
+
+
+def _aug_params(prm, sel_images):
+    from ._lib import AugParams
+    return (AugParams * len(sel_images))(*[prm[i] for i in sel_images])
+
+
+class _LoopIM:
+    """the ensemble stage of a writer: `run(subset, idx, x, ...)` on the pool (per-image members) or on the group's own ensemble"""
+
+    def __init__(self, models, pooled):
+        F = _F()
+        self.models, self.pooled, self.ensembles = models, pooled and len(models) <= 16, {}
+        self.pool = F.PoolIM(models) if self.pooled else None
+
+    def run(self, plan, subset, idx, x, thr, cmp_ge):
+        """-> (result dict, IM after the per-image random erosion / dilation)"""
+        F = _F()
+        if self.pooled:
+            r = self.pool.run(x, [plan[i][0] for i in idx], thr, cmp_ge, False, False)
+            return r, _var_morph(r["im"], plan, idx)
+        if subset not in self.ensembles:
+            self.ensembles[subset] = F.EnsembleIM([self.models[j] for j in subset])
+        r = self.ensembles[subset].run(x, thr, cmp_ge, False, False)
+        return r, _random_morph(r["im"], plan, idx)
+
+
 # ---------------------------------------------------------------------------------------------------
 # training data of the binary EvalNet from ensemble IM predictions (functions.py:3572-3670)
 # ---------------------------------------------------------------------------------------------------
@@ -71,40 +132,36 @@ def create_training_data_evalnet_im_binary(models, h, w, c, images_path, masks_p
     names = sorted(os.listdir(images_path))
     draw_kw = dict(brightness_range_alpha=brightness_range_alpha, brightness_range_beta=brightness_range_beta,
                    max_blur=max_blur, max_noise=max_noise, free_rotation=free_rotation, rng=rng, np_rng=np_rng)
-    rows, ensembles = [], {}
+    rows, stage = [], _LoopIM(models, POOLED)
     with F._pool() as pool:
         for nl in range(num_loops):
             plan = _draw_plan(rng, len(names), len(models), n_min_models, n_max_models)
+            prm = _draw_aug(plan, F.INFER_BATCH, draw_kw)
             loop_rows = {}
-            for subset, idx_all in _groups(plan).items():
-                if subset not in ensembles:
-                    ensembles[subset] = F.EnsembleIM([models[j] for j in subset])
-                for s in range(0, len(idx_all), F.INFER_BATCH):
-                    idx = idx_all[s:s + F.INFER_BATCH]
-                    x = torch.from_numpy(F.read_png_stack(pool, [os.path.join(images_path, names[i]) for i in idx], c)).cuda()
-                    gt = torch.from_numpy(F.read_png_stack(pool, [os.path.join(masks_path, names[i]) for i in idx], 1)).cuda()
-                    r = ensembles[subset].run(x.flip(-1).contiguous() if flip else x, F.THRESHOLD, False, False, False)
-                    im = _random_morph(r["im"], plan, idx)
-                    masks, img = r["masks"], x.clone()
-                    _im.block_apply(im, img, masks)
-                    pred, g = masks[:, 0] > 0, gt[..., 0] > 0
-                    inter = (pred & g).sum(dim=(1, 2)).cpu().numpy()
-                    union = (pred | g).sum(dim=(1, 2)).cpu().numpy()
-                    ious = inter / (union + 1e-7)
-                    mk = masks.permute(0, 2, 3, 1).contiguous()
-                    aug = torch.tensor([plan[i][3] for i in idx], device="cuda")
-                    sel = torch.nonzero(aug).flatten()
-                    if sel.numel():      # functions.py:3657-3658
-                        o, om = augment_batch(img[sel].contiguous(), mk[sel].contiguous(), draw_params(int(sel.numel()), **draw_kw))
-                        img[sel], mk[sel] = o, om
-                    img_np, mk_np = img.cpu().numpy(), mk.cpu().numpy()
-                    jobs = []
-                    for row, i in enumerate(idx):
-                        out_name = f"{names[i][:-4]}_aug_{nl}.png"
-                        loop_rows[i] = (out_name, round(float(ious[row]), 4))
-                        jobs.append((os.path.join(iout, out_name), img_np[row]))
-                        jobs.append((os.path.join(mout, out_name), mk_np[row, :, :, 0]))
-                    F.write_pngs_async(jobs)      # on the writer pool: the next batch's decode, network pass and augmentation run meanwhile
+            for subset, idx in _chunks(plan, F.INFER_BATCH, stage.pooled):
+                x = torch.from_numpy(F.read_png_stack(pool, [os.path.join(images_path, names[i]) for i in idx], c)).cuda()
+                gt = torch.from_numpy(F.read_png_stack(pool, [os.path.join(masks_path, names[i]) for i in idx], 1)).cuda()
+                r, im = stage.run(plan, subset, idx, x.flip(-1).contiguous() if flip else x, F.THRESHOLD, False)
+                masks, img = r["masks"], x.clone()
+                _im.block_apply(im, img, masks)
+                pred, g = masks[:, 0] > 0, gt[..., 0] > 0
+                inter = (pred & g).sum(dim=(1, 2)).cpu().numpy()
+                union = (pred | g).sum(dim=(1, 2)).cpu().numpy()
+                ious = inter / (union + 1e-7)
+                mk = masks.permute(0, 2, 3, 1).contiguous()
+                aug = torch.tensor([plan[i][3] for i in idx], device="cuda")
+                sel = torch.nonzero(aug).flatten()
+                if sel.numel():      # functions.py:3657-3658
+                    o, om = augment_batch(img[sel].contiguous(), mk[sel].contiguous(), _aug_params(prm, [i for i in idx if plan[i][3]]))
+                    img[sel], mk[sel] = o, om
+                img_np, mk_np = img.cpu().numpy(), mk.cpu().numpy()
+                jobs = []
+                for row, i in enumerate(idx):
+                    out_name = f"{names[i][:-4]}_aug_{nl}.png"
+                    loop_rows[i] = (out_name, round(float(ious[row]), 4))
+                    jobs.append((os.path.join(iout, out_name), img_np[row]))
+                    jobs.append((os.path.join(mout, out_name), mk_np[row, :, :, 0]))
+                F.write_pngs_async(jobs)      # on the writer pool: the next batch's decode, network pass and augmentation run meanwhile
             rows += [loop_rows[i] for i in range(len(names))]
     F.flush_writes()
     with open(os.path.join(main_output_path, "labels.csv"), "a", encoding="utf-8", newline="") as f:
@@ -173,44 +230,40 @@ def create_training_data_evalnet_miou_im_multiclass(models, h, w, c, num_classes
     names = sorted(os.listdir(images_path))
     draw_kw = dict(brightness_range_alpha=brightness_range_alpha, brightness_range_beta=brightness_range_beta,
                    max_blur=max_blur, max_noise=max_noise, free_rotation=free_rotation, rng=rng, np_rng=np_rng)
-    rows, ensembles = [], {}
+    rows, stage = [], _LoopIM(models, POOLED)
     with F._pool() as pool:
         for nl in range(num_loops):
             plan = _draw_plan(rng, len(names), len(models), n_min_models, n_max_models)
+            prm = _draw_aug(plan, F.INFER_BATCH, draw_kw)
             loop_rows = {}
-            for subset, idx_all in _groups(plan).items():
-                if subset not in ensembles:
-                    ensembles[subset] = F.EnsembleIM([models[j] for j in subset])
-                for s in range(0, len(idx_all), F.INFER_BATCH):
-                    idx = idx_all[s:s + F.INFER_BATCH]
-                    x = torch.from_numpy(F.read_png_stack(pool, [os.path.join(images_path, names[i]) for i in idx], c)).cuda()
-                    gts = list(pool.map(lambda i: F.read_png(os.path.join(masks_path, names[i]), 1)[..., 0], idx))
-                    r = ensembles[subset].run(x.flip(-1).contiguous() if flip else x, F.THRESHOLD, False, False, False)
-                    im = _random_morph(r["im"], plan, idx)
-                    masks, img = r["masks"], x.clone()
-                    _im.block_apply(im, img, masks)
-                    pred_np, im_np = masks[:, 0].cpu().numpy(), im.cpu().numpy()
-                    mk = masks.permute(0, 2, 3, 1).contiguous()
-                    sel = torch.nonzero(torch.tensor([plan[i][3] for i in idx], device="cuda")).flatten()
-                    if sel.numel():      # functions.py:3859-3860
-                        o, om = augment_batch(img[sel].contiguous(), mk[sel].contiguous(), draw_params(int(sel.numel()), **draw_kw))
-                        img[sel], mk[sel] = o, om
-                    img_np, mk_np = img.cpu().numpy(), mk.cpu().numpy()
-                    jobs = []
-                    for row, i in enumerate(idx):
-                        gt = gts[row]
-                        ious = compute_classwise_IoU(pred_np[row], gt, num_classes)
-                        counts = np.zeros(num_classes)
-                        bins = np.bincount(gt.ravel(), minlength=num_classes)
-                        counts[:len(bins)] += bins[:num_classes] if len(bins) > num_classes else bins
-                        gt_blocked = gt.copy()
-                        gt_blocked[im_np[row] > 0] = 0
-                        det = compute_classwise_detection_im(gt_blocked, num_classes, counts, 0.3)
-                        out_name = f"{names[i][:-4]}_aug_{nl}.png"
-                        loop_rows[i] = (out_name, *ious, *det)
-                        jobs.append((os.path.join(iout, out_name), img_np[row]))
-                        jobs.append((os.path.join(mout, out_name), mk_np[row, :, :, 0]))
-                    F.write_pngs_async(jobs)      # on the writer pool: the next batch's decode, network pass and augmentation run meanwhile
+            for subset, idx in _chunks(plan, F.INFER_BATCH, stage.pooled):
+                x = torch.from_numpy(F.read_png_stack(pool, [os.path.join(images_path, names[i]) for i in idx], c)).cuda()
+                gts = list(pool.map(lambda i: F.read_png(os.path.join(masks_path, names[i]), 1)[..., 0], idx))
+                r, im = stage.run(plan, subset, idx, x.flip(-1).contiguous() if flip else x, F.THRESHOLD, False)
+                masks, img = r["masks"], x.clone()
+                _im.block_apply(im, img, masks)
+                pred_np, im_np = masks[:, 0].cpu().numpy(), im.cpu().numpy()
+                mk = masks.permute(0, 2, 3, 1).contiguous()
+                sel = torch.nonzero(torch.tensor([plan[i][3] for i in idx], device="cuda")).flatten()
+                if sel.numel():      # functions.py:3859-3860
+                    o, om = augment_batch(img[sel].contiguous(), mk[sel].contiguous(), _aug_params(prm, [i for i in idx if plan[i][3]]))
+                    img[sel], mk[sel] = o, om
+                img_np, mk_np = img.cpu().numpy(), mk.cpu().numpy()
+                jobs = []
+                for row, i in enumerate(idx):
+                    gt = gts[row]
+                    ious = compute_classwise_IoU(pred_np[row], gt, num_classes)
+                    counts = np.zeros(num_classes)
+                    bins = np.bincount(gt.ravel(), minlength=num_classes)
+                    counts[:len(bins)] += bins[:num_classes] if len(bins) > num_classes else bins
+                    gt_blocked = gt.copy()
+                    gt_blocked[im_np[row] > 0] = 0
+                    det = compute_classwise_detection_im(gt_blocked, num_classes, counts, 0.3)
+                    out_name = f"{names[i][:-4]}_aug_{nl}.png"
+                    loop_rows[i] = (out_name, *ious, *det)
+                    jobs.append((os.path.join(iout, out_name), img_np[row]))
+                    jobs.append((os.path.join(mout, out_name), mk_np[row, :, :, 0]))
+                F.write_pngs_async(jobs)      # on the writer pool: the next batch's decode, network pass and augmentation run meanwhile
             rows += [loop_rows[i] for i in range(len(names))]
     F.flush_writes()
     with open(os.path.join(main_output_path, "labels.csv"), "a", encoding="utf-8", newline="") as f:
@@ -245,44 +298,37 @@ def create_training_data_evalnet_miou_im_hela(models, h, w, c, main_input_path, 
         os.makedirs(d, exist_ok=True)
     names = sorted(os.listdir(din["brightfield"]))
     rows = []
-    ensembles = {}
+    stage = _LoopIM(models, POOLED)
     with F._pool() as pool:
         for nl in range(num_loops):
             plan = _draw_plan(rng, len(names), len(models), n_min_models, n_max_models)
             loop_rows = {}
-            groups = _groups(plan)
-            for subset, idx_all in groups.items():
-                if subset not in ensembles:
-                    ensembles[subset] = F.EnsembleIM([models[j] for j in subset])
-                ens = ensembles[subset]
-                for s in range(0, len(idx_all), F.INFER_BATCH):
-                    idx = idx_all[s:s + F.INFER_BATCH]
-                    rd = lambda k: torch.from_numpy(np.stack(list(pool.map(
-                        lambda i: F.read_png(os.path.join(din[k], names[i]), 1), idx)), 0)).cuda()
-                    bf, gt = rd("brightfield"), torch.cat([rd("alive"), rd("dead"), rd("mod_position")], 3)
-                    r = ens.run(bf, 0.5, True, False, False)
-                    im = _random_morph(r["im"], plan, idx)     # erode first, then dilate (functions.py:3945-3953)
-                    masks = r["masks"]
-                    bf = bf.clone()
-                    _im.block_apply(im, bf, masks)
-                    pred = masks > 0
-                    g = gt.permute(0, 3, 1, 2) > 0
-                    inter = (pred & g).sum(dim=(2, 3)).cpu().numpy()
-                    union = (pred | g).sum(dim=(2, 3)).cpu().numpy()
-                    gt_nz = g.sum(dim=(2, 3)).cpu().numpy()
-                    ious = inter / (union + 1e-7)                       # get_IoU_binary, functions.py:1767-1788
-                    det = np.stack([gt_nz[:, 0] >= h * w * 0.01, gt_nz[:, 1] >= h * w * 0.01, gt_nz[:, 2] >= h * w * 0.001], 1)
-                    bf_np = bf.cpu().numpy()
-                    m_np = (masks > 0).to(torch.uint8).cpu().numpy()    # {0,1}: the uint8 wrap of `mask * 255`
-                    jobs = []
-                    for row, i in enumerate(idx):
-                        out_name = f"{names[i][:-4]}_aug_{nl}.png"
-                        loop_rows[i] = (out_name, ious[row, 0], ious[row, 1], ious[row, 2], int(det[row, 0]), int(det[row, 1]),
-                                        int(det[row, 2]))
-                        jobs.append((os.path.join(dout["brightfield"], out_name), bf_np[row, :, :, 0]))
-                        for k, key in enumerate(("alive", "dead", "mod_position")):
-                            jobs.append((os.path.join(dout[key], out_name), m_np[row, k]))
-                    F.write_pngs_async(jobs)      # on the writer pool: the next batch's decode, network pass and augmentation run meanwhile
+            for subset, idx in _chunks(plan, F.INFER_BATCH, stage.pooled):
+                rd = lambda k: torch.from_numpy(np.stack(list(pool.map(
+                    lambda i: F.read_png(os.path.join(din[k], names[i]), 1), idx)), 0)).cuda()
+                bf, gt = rd("brightfield"), torch.cat([rd("alive"), rd("dead"), rd("mod_position")], 3)
+                r, im = stage.run(plan, subset, idx, bf, 0.5, True)     # erode first, then dilate (functions.py:3945-3953)
+                masks = r["masks"]
+                bf = bf.clone()
+                _im.block_apply(im, bf, masks)
+                pred = masks > 0
+                g = gt.permute(0, 3, 1, 2) > 0
+                inter = (pred & g).sum(dim=(2, 3)).cpu().numpy()
+                union = (pred | g).sum(dim=(2, 3)).cpu().numpy()
+                gt_nz = g.sum(dim=(2, 3)).cpu().numpy()
+                ious = inter / (union + 1e-7)                       # get_IoU_binary, functions.py:1767-1788
+                det = np.stack([gt_nz[:, 0] >= h * w * 0.01, gt_nz[:, 1] >= h * w * 0.01, gt_nz[:, 2] >= h * w * 0.001], 1)
+                bf_np = bf.cpu().numpy()
+                m_np = (masks > 0).to(torch.uint8).cpu().numpy()    # {0,1}: the uint8 wrap of `mask * 255`
+                jobs = []
+                for row, i in enumerate(idx):
+                    out_name = f"{names[i][:-4]}_aug_{nl}.png"
+                    loop_rows[i] = (out_name, ious[row, 0], ious[row, 1], ious[row, 2], int(det[row, 0]), int(det[row, 1]),
+                                    int(det[row, 2]))
+                    jobs.append((os.path.join(dout["brightfield"], out_name), bf_np[row, :, :, 0]))
+                    for k, key in enumerate(("alive", "dead", "mod_position")):
+                        jobs.append((os.path.join(dout[key], out_name), m_np[row, k]))
+                F.write_pngs_async(jobs)      # on the writer pool: the next batch's decode, network pass and augmentation run meanwhile
             rows += [loop_rows[i] for i in range(len(names))]
     F.flush_writes()
     with open(os.path.join(main_output_path, "labels.csv"), "a", encoding="utf-8", newline="") as f:

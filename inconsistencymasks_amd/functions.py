@@ -457,6 +457,75 @@ class EnsembleIM:
                 "presence": presence}
 
 
+class PoolIM:
+    """A pool of up to 16 models and ONE workspace for per-image sub-ensembles: `.run()` is EnsembleIM's with a member set per
+    image (im.member_words).  Native UNet models take imk_unet_forward_im_members (every model runs once, on the images that use
+    it); duck-typed `.predict` models are predicted per pool model and go through imk_im_binary_members /
+    imk_im_multiclass_members.  binary: needed for duck-typed pools only (native plans know their head)."""
+
+    def __init__(self, models, binary=None):
+        self.models = list(models)
+        if not 1 <= len(self.models) <= 16:
+            raise ValueError("a model pool has 1 to 16 models")
+        self.native = _is_native(self.models)
+        self._ws = None
+        self._ws_batch = 0
+        if self.native:
+            import ctypes
+            self.plan = self.models[0].plan
+            for m in self.models:
+                m.ready_for_inference()
+            n = len(self.models)
+            self._params = (ctypes.c_void_p * n)(*[m.params.data_ptr() for m in self.models])
+            self._packed = (ctypes.c_void_p * n)(*[m.packed.data_ptr() for m in self.models])
+            self.binary = self.plan.act_out == "sigmoid"
+        else:
+            if binary is None:
+                raise TypeError("a pool of duck-typed models needs binary=True / False")
+            self.binary = bool(binary)
+
+    def run(self, x_u8, members, thr=0.5, cmp_ge=False, block_in=True, block_out=True, want_presence=False):
+        """x_u8 [B,H,W,C] uint8 device, members: B member words or index sets -> the dict of EnsembleIM.run (presence [N,B,K] over
+        the pool, 0 for non-members)."""
+        import ctypes
+        b = x_u8.shape[0]
+        n = len(self.models)
+        dev = x_u8.device
+        words = _im.member_words(members, b, n)
+        if not self.native:
+            preds = StackIM(self.models, self.binary)._stack(x_u8)
+            if self.binary:
+                r = _im.im_binary_members(preds, words, thr, cmp_ge, x_u8, block_in, block_out)
+                r["presence"] = None
+                return r
+            r = _im.im_multiclass_members(preds, words, x_u8, block_in, block_out, want_presence=want_presence)
+            return {"img_out": r["img_out"], "masks": r["final"][:, None], "im": r["im"], "im_size": r["im_size"][:, None],
+                    "pred_size": torch.zeros((b, 1), dtype=torch.int64, device=dev), "presence": r["presence"]}
+        p = self.plan
+        if self._ws is None or self._ws_batch < b:
+            nbytes = lib.imk_unet_forward_im_members_workspace_bytes(p.ptr, n, b, min(n, 3))
+            if nbytes < 0:
+                check(int(nbytes), "imk_unet_forward_im_members_workspace_bytes")
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            self._ws_batch = b
+        kb = p.n_out if self.binary else 1
+        masks = torch.empty((b, kb, p.h, p.w), dtype=torch.uint8, device=dev)
+        im = torch.empty((b, p.h, p.w), dtype=torch.uint8, device=dev)
+        im_size = torch.empty((b, kb), dtype=torch.int64, device=dev)
+        pred_size = torch.zeros((b, kb), dtype=torch.int64, device=dev)
+        presence = torch.empty((n, b, p.n_out), dtype=torch.uint8, device=dev) if (want_presence and not self.binary) else None
+        img_out = torch.empty_like(x_u8)
+        x_u8 = x_u8.contiguous()
+        check(lib.imk_unet_forward_im_members(p.ptr, n, self._params, self._packed, x_u8.data_ptr(), b,
+                                              words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), float(thr),
+                                              int(bool(cmp_ge)), x_u8.data_ptr(), int(bool(block_in)), int(bool(block_out)),
+                                              img_out.data_ptr(), masks.data_ptr(), im.data_ptr(), im_size.data_ptr(),
+                                              pred_size.data_ptr(), 0 if presence is None else presence.data_ptr(),
+                                              self._ws.data_ptr(), self._ws.numel(), _stream()), "imk_unet_forward_im_members")
+        return {"img_out": img_out, "masks": masks, "im": im, "im_size": im_size, "pred_size": pred_size,
+                "presence": presence}
+
+
 class StackIM:
     """The same `.run()` as EnsembleIM for duck-typed models (anything with `.predict(x)` like a Keras model, called once
     per image with a [1,H,W,C] batch exactly as functions.py:3157 / :3224 do): the probability stack goes through
@@ -465,7 +534,7 @@ class StackIM:
     def __init__(self, models, binary):
         self.models, self.binary = list(models), binary
 
-    def run(self, x_u8, thr=0.5, cmp_ge=False, block_in=True, block_out=True, want_presence=False):
+    def _stack(self, x_u8):
         outs = []
         for m in self.models:
             if hasattr(m, "predict_device"):
@@ -474,7 +543,10 @@ class StackIM:
                 xs = x_u8.cpu().numpy()
                 p = np.concatenate([np.asarray(m.predict(xs[i:i + 1]), dtype=np.float32) for i in range(len(xs))], 0)
                 outs.append(torch.from_numpy(p).cuda())
-        preds = torch.stack(outs, 0).contiguous()
+        return torch.stack(outs, 0).contiguous()
+
+    def run(self, x_u8, thr=0.5, cmp_ge=False, block_in=True, block_out=True, want_presence=False):
+        preds = self._stack(x_u8)
         if self.binary:
             r = _im.im_binary(preds, thr, cmp_ge, x_u8, block_in, block_out)
             r["presence"] = None

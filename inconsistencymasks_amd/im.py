@@ -1,5 +1,6 @@
-"""Host wrappers of the fused IM kernels (imk_im_binary / imk_im_multiclass / imk_morph / imk_block_apply).
-torch is used for device memory and streams only."""
+"""Host wrappers of the fused IM kernels (imk_im_binary / imk_im_multiclass / imk_morph / imk_block_apply and their per-image
+forms imk_im_binary_members / imk_im_multiclass_members / imk_morph_var).  torch is used for device memory and streams only."""
+import numpy as np
 import torch
 
 from ._lib import check, lib
@@ -65,6 +66,87 @@ def im_multiclass(probs, img=None, block_in=True, block_out=True, want_presence=
                                 final.data_ptr(), im.data_ptr(), im_size.data_ptr(), _ptr(presence),
                                 _stream()), "imk_im_multiclass")
     return {"final": final, "im": im, "im_size": im_size, "presence": presence, "img_out": img_out}
+
+
+def member_words(members, batch, n_models):
+    """per-image member words as a uint32 numpy array [B]: bit n set = model n of the pool votes for the image.  Accepts the words
+    themselves or, per image, an iterable of model indices."""
+    if n_models < 1 or n_models > 16:
+        raise ValueError("a model pool has 1 to 16 models")
+    words = np.zeros(batch, dtype=np.uint32)
+    if len(members) != batch:
+        raise ValueError(f"{len(members)} member sets for {batch} images")
+    for i, m in enumerate(members):
+        if isinstance(m, (int, np.integer)):
+            words[i] = int(m) & 0xFFFFFFFF
+        else:
+            for j in m:
+                if not 0 <= int(j) < n_models:
+                    raise ValueError(f"member {j} outside a pool of {n_models}")
+                words[i] |= np.uint32(1 << int(j))
+    return words
+
+
+def im_binary_members(preds, members, thr=0.5, cmp_ge=False, img=None, block_in=True, block_out=True):
+    """im_binary over per-image sub-ensembles: preds [N,B,H,W,Kb] holds the whole pool (N <= 16), members (member_words) says which
+    models vote for which image.  Semantics: include/imk.h, imk_im_binary_members."""
+    if preds.dtype != torch.float32 or preds.dim() != 5 or not preds.is_cuda:
+        raise TypeError("preds must be a float32 CUDA tensor [N,B,H,W,Kb]")
+    preds = preds.contiguous()
+    n, b, h, w, kb = preds.shape
+    dev = preds.device
+    words = torch.from_numpy(member_words(members, b, n).view(np.int32)).to(dev)
+    img = _dev_u8(img, dev)
+    c = 0 if img is None else img.shape[-1]
+    masks = torch.empty((b, kb, h, w), dtype=torch.uint8, device=dev)
+    im = torch.empty((b, h, w), dtype=torch.uint8, device=dev)
+    im_size = torch.empty((b, kb), dtype=torch.int64, device=dev)
+    pred_size = torch.empty((b, kb), dtype=torch.int64, device=dev)
+    img_out = None if img is None else torch.empty_like(img)
+    check(lib.imk_im_binary_members(preds.data_ptr(), words.data_ptr(), n, b, h, w, kb, float(thr), int(bool(cmp_ge)),
+                                    _ptr(img), c, int(bool(block_in)), int(bool(block_out)),
+                                    _ptr(img_out), masks.data_ptr(), im.data_ptr(),
+                                    im_size.data_ptr(), pred_size.data_ptr(), _stream()), "imk_im_binary_members")
+    return {"masks": masks, "im": im, "im_size": im_size, "pred_size": pred_size, "img_out": img_out}
+
+
+def im_multiclass_members(probs, members, img=None, block_in=True, block_out=True, want_presence=True):
+    """im_multiclass over per-image sub-ensembles (see im_binary_members); presence [N,B,K] is 0 in the rows of non-members."""
+    if probs.dtype != torch.float32 or probs.dim() != 5 or not probs.is_cuda:
+        raise TypeError("probs must be a float32 CUDA tensor [N,B,H,W,K]")
+    probs = probs.contiguous()
+    n, b, h, w, k = probs.shape
+    dev = probs.device
+    words = torch.from_numpy(member_words(members, b, n).view(np.int32)).to(dev)
+    img = _dev_u8(img, dev)
+    c = 0 if img is None else img.shape[-1]
+    final = torch.empty((b, h, w), dtype=torch.uint8, device=dev)
+    im = torch.empty((b, h, w), dtype=torch.uint8, device=dev)
+    im_size = torch.empty((b,), dtype=torch.int64, device=dev)
+    presence = torch.empty((n, b, k), dtype=torch.uint8, device=dev) if want_presence else None
+    img_out = None if img is None else torch.empty_like(img)
+    check(lib.imk_im_multiclass_members(probs.data_ptr(), words.data_ptr(), n, b, h, w, k, _ptr(img), c,
+                                        int(bool(block_in)), int(bool(block_out)), _ptr(img_out),
+                                        final.data_ptr(), im.data_ptr(), im_size.data_ptr(), _ptr(presence),
+                                        _stream()), "imk_im_multiclass_members")
+    return {"final": final, "im": im, "im_size": im_size, "presence": presence, "img_out": img_out}
+
+
+def morph_var(mask, ksizes, op):
+    """morph with one window per image: ksizes [B] ints, odd and at most 31, 0 = the image is copied (imk_morph_var)."""
+    mask = mask.contiguous()
+    b, h, w = mask.shape
+    ks = [int(k) for k in ksizes]
+    if len(ks) != b:
+        raise ValueError(f"{len(ks)} window sizes for {b} images")
+    for k in ks:
+        if k < 0 or k > 31 or (k and k % 2 == 0):
+            raise ValueError(f"window size {k}: 0 (copy) or odd and at most 31")
+    kd = torch.tensor(ks, dtype=torch.int32).to(mask.device)
+    out = torch.empty_like(mask)
+    check(lib.imk_morph_var(mask.data_ptr(), out.data_ptr(), b, h, w, kd.data_ptr(), 0 if op == "erode" else 1,
+                            _stream()), "imk_morph_var")
+    return out
 
 
 def morph(mask, ksize, op):
