@@ -244,7 +244,7 @@ struct ImkHeadImArgs {
 bool imk_head_im_supported(const ImkHeadImArgs &a);
 int imk_launch_head_im(const ImkHeadImArgs &a, hipStream_t stream);
 
-// ---- fused head + inconsistency mask over per-image members of a model pool (imk_members.hip) --------------------------------
+// ---- fused head + inconsistency mask over per-image members of a model pool (imk_im.hip) -----------------------------------
 #define IMK_MEMBERS_MAX_POOL 16
 struct ImkHeadImMembersArgs {
     const f16 *z[IMK_MEMBERS_MAX_POOL];          // model n's last decoder conv output [count_n,H,W,cs]: the images that use it

@@ -1,4 +1,4 @@
-// The LDS finish of the IM kernels (imk_im.hip, imk_members.hip): a workgroup's label / mask bytes staged in LDS leave the CU as
+// The LDS finish of the IM kernels (the bodies of imk_imrule.h): a workgroup's label / mask bytes staged in LDS leave the CU as
 // 16-byte stores, the image is blocked on the way through, and the per-image sizes take one global atomic per workgroup and map.
 #pragma once
 #include "imk_common.h"

@@ -4,6 +4,7 @@
 // Everything is enqueued on the caller's stream; nothing here allocates or synchronises.
 #include <atomic>
 #include <cstdio>
+#include <vector>
 #include "imk_net.h"
 #include "imk_head.h"
 #include "imk_switches.h"
@@ -340,23 +341,31 @@ struct EnsembleHeads {
     const float **sc, **sh, **w, **bias;
 };
 
-// The N forward passes of an ensemble (imk_unet_forward_im, imk_unet_forward_vote).  `slab` bytes per model at the start of the
-// workspace, then one activation workspace per concurrent stream.  heads != NULL (fused): the last decoder activation of model m goes
-// to its head slab and `heads` receives the pointers the fused kernel reads; no head launch.  heads == NULL: model m's fp32
-// probabilities go to base + m * B*H*W*K*4 (the contiguous stack [N,B,H,W,K]).  Everything ends joined to `main_stream`.
-static int run_ensemble_forwards(const imk_unet_plan *plan, const Topo &topo, const Ws &ws, int n_models, const float *const *params,
-                                 const void *const *packed, const uint8_t *x, int batch, size_t slab, uint8_t *base,
-                                 int64_t workspace_bytes, const EnsembleHeads *heads, hipStream_t main_stream) {
+// One forward of an ensemble call: model `model` (its index in params / packed / heads) on `batch` images -- the caller's input
+// batch, or, with `gather`, the rows gather[0 .. batch) of it, compacted into the stream's input buffer first.
+struct ForwardJob {
+    int model, batch;
+    const int64_t *gather;
+    const Ws *ws;        // the activation workspace at this batch
+    f16 *slab;           // fused: the model's head slab (its last decoder activation)
+    float *probs;        // unfused: its fp32 probabilities
+};
+
+// The forward passes of an ensemble (imk_unet_forward_im, _im_members, _im_depth, _vote), a model nobody uses simply absent.  `regions`:
+// per concurrent stream `per_stream` bytes, an input buffer of `xbuf` bytes (jobs with a gather list) and then an activation workspace.
+// heads != NULL (fused): the last decoder activation of a job goes to its head slab and `heads` receives the pointers the fused
+// kernel reads; no head launch.  heads == NULL: its fp32 probabilities go to `probs`.  Everything ends joined to `main_stream`.
+static int run_ensemble_forwards(const imk_unet_plan *plan, const Topo &topo, const ForwardJob *jobs, int n_jobs,
+                                 const float *const *params, const void *const *packed, const uint8_t *x, uint8_t *regions,
+                                 size_t per_stream, size_t xbuf, int64_t regions_bytes, const EnsembleHeads *heads,
+                                 hipStream_t main_stream) {
     const imk_unet_cfg &cf = plan->cfg;
-    const bool fused = heads != nullptr;
-    // the unfused probability stack must be contiguous [N,B,H,W,K]: only the last slab may be padded
-    const size_t probs_exact = (size_t)batch * cf.h * cf.w * cf.n_out * sizeof(float);
-    // The models are independent until the IM stage: with room for one activation workspace per stream (the caller
-    // passes slabs + k * imk_unet_workspace_bytes, k <= 1 + MAX_SIDE) they run on k streams side by side -- the deep
-    // layers of one model fill the gaps of the other's.  With room for one only, they run back to back.
+    // The models are independent until the IM stage: with room for one region per stream (the caller passes its fixed part
+    // + k regions, k <= 1 + MAX_SIDE) they run on k streams side by side -- the deep layers of one model fill the gaps of the
+    // other's.  With room for one only, they run back to back.
     const int max_streams = 1 + imk_unet_plan::MAX_SIDE;
-    int n_slabs = (int)(((size_t)workspace_bytes - slab * n_models) / ws.total);
-    if (n_slabs > n_models) n_slabs = n_models;
+    int n_slabs = (int)((size_t)regions_bytes / per_stream);
+    if (n_slabs > n_jobs) n_slabs = n_jobs;
     if (n_slabs > max_streams) n_slabs = max_streams;
     if (n_slabs > 1 && (plan->dbg_single_stream || !ensure_side_streams(plan, n_slabs - 1))) n_slabs = 1;
     if (n_slabs > 1) {
@@ -364,19 +373,26 @@ static int run_ensemble_forwards(const imk_unet_plan *plan, const Topo &topo, co
         for (int s = 1; s < n_slabs; ++s) IMK_HIP(hipStreamWaitEvent(plan->side[s - 1], plan->ev_fork[0], 0));
     }
     const ImkLayer &o = plan->layers[topo.out];
-    for (int m = 0; m < n_models; ++m) {
-        const int sl = m % n_slabs;
-        Ctx c{plan, ws, base + slab * n_models + ws.total * sl, params[m], (const uint8_t *)packed[m], batch, false,
-              sl == 0 ? main_stream : plan->side[sl - 1]};
-        c.x_in[0] = x;
-        if (fused) {    // the last decoder activation goes to the model's head slab; no head launch
+    const int64_t row_img = (int64_t)cf.h * cf.w * cf.c_in;
+    for (int i = 0; i < n_jobs; ++i) {
+        const ForwardJob &j = jobs[i];
+        const int sl = i % n_slabs, m = j.model;
+        hipStream_t st = sl == 0 ? main_stream : plan->side[sl - 1];
+        uint8_t *region = regions + per_stream * sl;
+        if (j.gather) {
+            int rc = imk_gather_pairs(x, row_img, nullptr, 0, 0, 0, nullptr, j.gather, j.batch, region, nullptr, st);
+            if (rc) return rc;
+        }
+        Ctx c{plan, *j.ws, region + xbuf, params[m], (const uint8_t *)packed[m], j.batch, false, st};
+        c.x_in[0] = j.gather ? region : x;
+        if (heads) {    // the last decoder activation goes to the model's head slab; no head launch
             c.ovr_conv = topo.d_c1[3];
-            c.ovr_out = reinterpret_cast<f16 *>(base + slab * m);
+            c.ovr_out = j.slab;
             heads->z[m] = c.ovr_out;
             heads->sc[m] = c.bn_scale(topo.d_bnb[3]); heads->sh[m] = c.bn_shift(topo.d_bnb[3]);
             heads->w[m] = params[m] + o.off_w; heads->bias[m] = params[m] + o.off_b;
         }
-        int rc = run_forward(c, topo, fused ? nullptr : (float *)(base + probs_exact * m), nullptr);
+        int rc = run_forward(c, topo, heads ? nullptr : j.probs, nullptr);
         if (rc) return rc;
     }
     for (int s = 1; s < n_slabs; ++s) {
@@ -384,6 +400,22 @@ static int run_ensemble_forwards(const imk_unet_plan *plan, const Topo &topo, co
         IMK_HIP(hipStreamWaitEvent(main_stream, plan->ev_join[s - 1], 0));
     }
     return IMK_OK;
+}
+
+// Every model on the whole batch.  `slab` bytes per model at the start of the workspace, then one activation workspace per concurrent
+// stream; unfused, model m's probabilities go to base + m * B*H*W*K*4 (the contiguous stack [N,B,H,W,K]: only the last slab may be
+// padded).
+static int run_ensemble_forwards(const imk_unet_plan *plan, const Topo &topo, const Ws &ws, int n_models, const float *const *params,
+                                 const void *const *packed, const uint8_t *x, int batch, size_t slab, uint8_t *base,
+                                 int64_t workspace_bytes, const EnsembleHeads *heads, hipStream_t main_stream) {
+    const imk_unet_cfg &cf = plan->cfg;
+    const size_t probs_exact = (size_t)batch * cf.h * cf.w * cf.n_out * sizeof(float);
+    std::vector<ForwardJob> jobs;
+    jobs.reserve(n_models);
+    for (int m = 0; m < n_models; ++m)
+        jobs.push_back({m, batch, nullptr, &ws, reinterpret_cast<f16 *>(base + slab * m), (float *)(base + probs_exact * m)});
+    return run_ensemble_forwards(plan, topo, jobs.data(), n_models, params, packed, x, base + slab * n_models, ws.total, 0,
+                                 workspace_bytes - (int64_t)(slab * n_models), heads, main_stream);
 }
 
 extern "C" int imk_unet_forward_im(const imk_unet_plan *plan, int n_models, const float *const *params,
@@ -422,7 +454,7 @@ extern "C" int imk_unet_forward_im(const imk_unet_plan *plan, int n_models, cons
 // Ensemble inference + IM over per-image members of a model pool.  Workspace: [member words u32 [B] | image lists int64 [N][B] |
 // rows int32 [N][B] | N head slabs | per concurrent stream: a compacted input batch and an activation workspace].  Fused: model n
 // runs on the images that use it (gathered by its list) and leaves their last decoder activations in its slab; one head + IM kernel
-// (imk_members.hip) reads, for image b, the slabs of b's members at row[n][b].  Unfused (shapes the kernel does not cover, more than
+// (imk_im.hip) reads, for image b, the slabs of b's members at row[n][b].  Unfused (shapes the kernel does not cover, more than
 // 8 members in some image, imk_debug_materialize(1)): every model that anybody uses runs on the whole batch into the fp32 stack
 // [N,B,H,W,K] at the start of the slabs, then imk_im_*_members.
 struct MembersLayout {
@@ -472,7 +504,6 @@ extern "C" int imk_unet_forward_im_members(const imk_unet_plan *plan, int n_mode
     int *d_row = (int *)(base + lay.row);
     hipStream_t main_stream = (hipStream_t)stream_;
     const Topo topo = make_topo(plan);
-    const ImkLayer &o = plan->layers[topo.out];
     ImkHeadImMembersArgs ha{};
     ha.members = d_members; ha.row = d_row;
     ha.n_models = n_models; ha.cin = cf.ch[0]; ha.cs = imk_pad8(cf.ch[0]); ha.K = cf.n_out; ha.softmax = cf.act_out;
@@ -480,13 +511,20 @@ extern "C" int imk_unet_forward_im_members(const imk_unet_plan *plan, int n_mode
     ha.block_in = block_in; ha.block_out = block_out; ha.img_out = img_out; ha.masks_out = masks_out; ha.im_out = im_out;
     ha.im_size = im_size; ha.pred_size = pred_size; ha.presence = presence;
     const bool fused = !plan->dbg_materialize && imk_head_im_members_supported(ha, max_members);
-    // a model's forward at its own batch: the activation workspace of a smaller batch fits the full batch's
+    // Every model that somebody uses, fused on its own images (gathered by its list unless it has them all; the activation
+    // workspace of a smaller batch fits the full batch's), unfused on the whole batch.
     Ws ws_of[IMK_MEMBERS_MAX_POOL];
     const Ws ws_full = make_ws(plan, batch, 0);
+    const size_t probs_exact = (size_t)batch * cf.h * cf.w * cf.n_out * sizeof(float);
+    ForwardJob jobs[IMK_MEMBERS_MAX_POOL];
+    int n_jobs = 0;
     for (int n = 0; n < n_models; ++n) {
-        if (!count[n]) continue;
-        ws_of[n] = (fused && count[n] < batch) ? make_ws(plan, count[n], 0) : ws_full;
+        if (!count[n]) continue;        // nobody uses this model
+        const int nb = fused ? count[n] : batch;
+        ws_of[n] = nb < batch ? make_ws(plan, nb, 0) : ws_full;
         if (ws_of[n].total > ws_full.total) return IMK_EWORKSPACE;
+        jobs[n_jobs++] = {n, nb, nb < batch ? d_list + (size_t)n * batch : nullptr, &ws_of[n],
+                          reinterpret_cast<f16 *>(base + lay.slabs + lay.slab * n), (float *)(base + lay.slabs + probs_exact * n)};
     }
     imk_launch_members_upload(members_host, batch, d_members, main_stream);
     IMK_LAUNCH_CHECK();
@@ -494,48 +532,10 @@ extern "C" int imk_unet_forward_im_members(const imk_unet_plan *plan, int n_mode
         imk_launch_members_lists(d_members, n_models, batch, d_list, d_row, main_stream);
         IMK_LAUNCH_CHECK();
     }
-    const int max_streams = 1 + imk_unet_plan::MAX_SIDE;
-    int n_used = 0;
-    for (int n = 0; n < n_models; ++n) n_used += count[n] > 0;
-    int n_slabs = (int)(((size_t)workspace_bytes - lay.fixed) / lay.per_stream);
-    if (n_slabs > n_used) n_slabs = n_used;
-    if (n_slabs > max_streams) n_slabs = max_streams;
-    if (n_slabs > 1 && (plan->dbg_single_stream || !ensure_side_streams(plan, n_slabs - 1))) n_slabs = 1;
-    if (n_slabs > 1) {
-        IMK_HIP(hipEventRecord(plan->ev_fork[0], main_stream));
-        for (int s = 1; s < n_slabs; ++s) IMK_HIP(hipStreamWaitEvent(plan->side[s - 1], plan->ev_fork[0], 0));
-    }
-    const size_t probs_exact = (size_t)batch * cf.h * cf.w * cf.n_out * sizeof(float);
-    const int64_t row_img = (int64_t)cf.h * cf.w * cf.c_in;
-    int used = 0;
-    for (int n = 0; n < n_models; ++n) {
-        if (!count[n]) continue;        // nobody uses this model
-        const int sl = used++ % n_slabs;
-        hipStream_t st = sl == 0 ? main_stream : plan->side[sl - 1];
-        uint8_t *region = base + lay.fixed + lay.per_stream * sl;
-        const int nb = fused ? count[n] : batch;
-        const uint8_t *xin = x;
-        if (nb < batch) {
-            int rc = imk_gather_pairs(x, row_img, nullptr, 0, 0, 0, nullptr, d_list + (size_t)n * batch, nb, region, nullptr, st);
-            if (rc) return rc;
-            xin = region;
-        }
-        Ctx c{plan, ws_of[n], region + lay.xbuf, params[n], (const uint8_t *)packed[n], nb, false, st};
-        c.x_in[0] = xin;
-        if (fused) {    // the last decoder activation goes to the model's head slab; no head launch
-            c.ovr_conv = topo.d_c1[3];
-            c.ovr_out = reinterpret_cast<f16 *>(base + lay.slabs + lay.slab * n);
-            ha.z[n] = c.ovr_out;
-            ha.sc[n] = c.bn_scale(topo.d_bnb[3]); ha.sh[n] = c.bn_shift(topo.d_bnb[3]);
-            ha.w[n] = params[n] + o.off_w; ha.bias[n] = params[n] + o.off_b;
-        }
-        int rc = run_forward(c, topo, fused ? nullptr : (float *)(base + lay.slabs + probs_exact * n), nullptr);
-        if (rc) return rc;
-    }
-    for (int s = 1; s < n_slabs; ++s) {
-        IMK_HIP(hipEventRecord(plan->ev_join[s - 1], plan->side[s - 1]));
-        IMK_HIP(hipStreamWaitEvent(main_stream, plan->ev_join[s - 1], 0));
-    }
+    const EnsembleHeads heads{ha.z, ha.sc, ha.sh, ha.w, ha.bias};
+    int rc = run_ensemble_forwards(plan, topo, jobs, n_jobs, params, packed, x, base + lay.fixed, lay.per_stream, lay.xbuf,
+                                   workspace_bytes - (int64_t)lay.fixed, fused ? &heads : nullptr, main_stream);
+    if (rc) return rc;
     if (fused) return imk_launch_head_im_members(ha, max_members, main_stream);
     const float *stack = (const float *)(base + lay.slabs);
     if (cf.act_out == 0)

@@ -110,18 +110,10 @@ __global__ __launch_bounds__(256) void vote_head_sigmoid_kernel(ImkVoteHeadArgs 
             for (int j = 0; j < 4; ++j)
 #pragma unroll
                 for (int q = 0; q < CS / 8; ++q) r[j][q] = *reinterpret_cast<const f16x8 *>(a.z[n] + (p + j) * CS + q * 8);
-            const float *s_sc = hn + K * CS + K, *s_sh = s_sc + CS;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 float xin[CS];
-#pragma unroll
-                for (int q = 0; q < CS / 8; ++q)
-#pragma unroll
-                    for (int e = 0; e < 8; e += 2) {                                                                      // = head_input
-                        const f16x2 r2 = imk_affine2(f16x2{r[j][q][e], r[j][q][e + 1]}, f32x2{s_sc[q * 8 + e], s_sc[q * 8 + e + 1]},
-                                                     f32x2{s_sh[q * 8 + e], s_sh[q * 8 + e + 1]});
-                        xin[q * 8 + e] = (float)r2[0]; xin[q * 8 + e + 1] = (float)r2[1];
-                    }
+                head_input_regs<CS>(r[j], hn, K, xin);
 #pragma unroll
                 for (int k = 0; k < KB; ++k) {
                     const float v = head_sigmoid(head_logit<CS>(xin, hn, K, k));

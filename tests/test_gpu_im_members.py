@@ -128,6 +128,47 @@ def test_every_bit_set_is_the_whole_ensemble_kernel(name):
         eq(got[key], want[key], key)
 
 
+# The generic (odd-size) kernels: 35 x 21 and 17 x 9 are no multiple of 4 pixels, and Kb 2 takes the generic kernel at any size.
+@pytest.mark.parametrize("kind,n,b,h,w,k", [("binary", 5, 3, 35, 21, 1), ("binary", 5, 3, 35, 21, 2), ("multi", 5, 3, 17, 9, 4)])
+def test_ragged_stacks_are_the_whole_ensemble_kernel_on_the_members(kind, n, b, h, w, k):
+    from inconsistencymasks_amd import im as IM
+    rng = np.random.default_rng(1000 * h + 10 * w + k)
+    # the models share a base so that agreement and disagreement both occur
+    stack = (0.6 * rng.random((1, b, h, w, k)) + 0.4 * rng.random((n, b, h, w, k))).astype(np.float32)
+    img_np = rng.integers(1, 256, (b, h, w, 3), dtype=np.uint8)
+    img = dev(img_np)
+
+    def whole(s):
+        return IM.im_multiclass(dev(s), img, True, True) if kind == "multi" else IM.im_binary(dev(s), 0.5, k == 2, img, True, True)
+
+    def members(words):
+        if kind == "multi":
+            return IM.im_multiclass_members(dev(stack), words, img, True, True)
+        return IM.im_binary_members(dev(stack), words, 0.5, k == 2, img, True, True)
+    got, want = members(np.full(b, (1 << n) - 1, np.uint32)), whole(stack)
+    assert set(got) == set(want)
+    for key in want:
+        eq(got[key], want[key], f"all bits: {key}")
+    # every image under every word: the whole-ensemble kernel on the word's models, image by image
+    words = [0b101, 1 << (n - 1), 0]
+    sub = {word: (MC.member_list(word, n), whole(stack[MC.member_list(word, n)])) for word in words if word}
+    for shift in range(b):
+        per_image = [words[(i + shift) % len(words)] for i in range(b)]
+        got = members(np.array(per_image, np.uint32))
+        for i, word in enumerate(per_image):
+            for key in got:
+                row = got[key][:, i] if key == "presence" else got[key][i]
+                if word == 0:                                # nobody votes: all zero, the image copied
+                    eq(row, img_np[i] if key == "img_out" else torch.zeros_like(row), f"word 0, image {i}: {key}")
+                    continue
+                mem, ref = sub[word]
+                if key == "presence":
+                    eq(row[mem], ref[key][:, i], f"word {word:#b}, image {i}: presence of the members")
+                    assert not row[[j for j in range(n) if j not in mem]].any(), "presence of a non-member"
+                else:
+                    eq(row, ref[key][i], f"word {word:#b}, image {i}: {key}")
+
+
 def test_wrappers_refuse_bad_members_before_upload():
     from inconsistencymasks_amd import im as IM
     with pytest.raises(ValueError):
