@@ -543,6 +543,16 @@ IMK_API int imk_eval_depth(const float *probs, const uint8_t *gt, int batch, int
  * "a.c1", "a.bn", the same with "b.", "m1.c3", "m1.c1", "m1.bn" ... "m5.bn", then "dense" or "iou", "detection"
  * (Dense kernels [C, n_out] + bias, reported as 1x1 convs); parameter order = Keras creation order. */
 IMK_API int imk_evalnet_plan_create(const imk_evalnet_cfg *cfg, imk_unet_plan **out);
+/* The late-fusion EvalNet, get_evalnet_miou_v2 (evalnet.py:76-106).  Same blocks, other wiring: each tower is input_block at
+ * ch[0] + FOUR conv_blocks at ch[0..3]; the towers' pooled outputs (H/16 x W/16, ch[3] channels) are ADDED -- two fp16 tensors,
+ * the exact sum rounded to fp16 once, as Keras' Add layer does under mixed_float16; three conv_blocks at ch[2], ch[3], ch[4]
+ * follow, then GlobalAvgPool2D and the heads 'iou' and 'detection'.  The cfg struct is the one above: two_heads must be 1, h and w
+ * even and >= 128 (seven poolings; odd rows / columns dropped), ch[3] a multiple of 8; every other limit as
+ * imk_evalnet_plan_create.  Layer names: "a.in.c", "a.in.bn", "a1.c3", "a1.c1", "a1.bn" ... "a4.bn", the same with "b",
+ * "m1.c3" ... "m3.bn", "iou", "detection"; parameter order = Keras creation order (tower A completely, tower B, trunk, heads).
+ * Every imk_evalnet_* call below takes such a plan and does the same job for it; imk_evalnet_forward_candidates then runs ALL of
+ * the image tower (about half of the network) once per image.  Plans made by imk_evalnet_plan_create run the launches they always ran. */
+IMK_API int imk_evalnet_v2_plan_create(const imk_evalnet_cfg *cfg, imk_unet_plan **out);
 IMK_API int64_t imk_evalnet_workspace_bytes(const imk_unet_plan *plan, int batch, int mode /* 0 inference, 1 training */);
 
 /* out [B, n_heads*n_out] f32 sigmoid outputs (two heads: iou units first, then detection units); inference-mode BN */
@@ -559,7 +569,10 @@ IMK_API int imk_evalnet_fwd_bwd(const imk_unet_plan *plan, float *params, void *
                         const uint8_t *xb, const float *y, int batch, float *out, float *grads, float *stats,
                         void *workspace, int64_t workspace_bytes, void *stream);
 
-/* Debug/parity: like imk_unet_tensor_info, for EvalNet plans */
+/* Debug/parity: like imk_unet_tensor_info, for EvalNet plans.  Two more values of `which`:
+ *   3  the INPUT of the trunk's first conv ("m1.c3"): the towers' concatenation, or for a v2 plan their sum (c = its channels)
+ *   4  a BatchNorm layer's fp32 scale[c_stride] | shift[c_stride] as the kernels apply them (h = 1, w = 2): mode 0 the folded
+ *      moving statistics, and byte_offset is into the PACKED buffer; mode 1 the last pass's batch statistics, in the workspace */
 IMK_API int imk_evalnet_tensor_info(const imk_unet_plan *plan, int batch, int mode, int layer_idx, int which,
                             int64_t *byte_offset, int *h, int *w, int *c, int *c_stride);
 

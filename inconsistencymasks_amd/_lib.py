@@ -102,6 +102,7 @@ SIGNATURES = {
     "imk_unet_consistency_fwd_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
                                              c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "imk_evalnet_plan_create": (c_int, [ctypes.POINTER(EvalnetCfg), ctypes.POINTER(c_void_p)]),
+    "imk_evalnet_v2_plan_create": (c_int, [ctypes.POINTER(EvalnetCfg), ctypes.POINTER(c_void_p)]),
     "imk_evalnet_workspace_bytes": (c_int64, [c_void_p, c_int, c_int]),
     "imk_evalnet_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64,
                                     c_void_p]),

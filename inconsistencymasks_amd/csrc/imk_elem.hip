@@ -596,6 +596,37 @@ __global__ __launch_bounds__(256) void concat_pool_kernel(const f16 *__restrict_
     *reinterpret_cast<f16x8 *>(cat + (size_t)pix * (csa + csb) + c8 * 8) = o;
 }
 
+// add([towerA, towerB]) of the two towers' BatchNorm + MaxPooling2D outputs (evalnet.py:92-96, get_evalnet_miou_v2): one thread
+// per (pooled pixel, 8-channel chunk).  Both towers have cs channels; their last Conv1x1 outputs are [.., H, W, cs] and the
+// sum is [B, H/2, W/2, cs] -- H and W are the SOURCE size, whose odd last row / column the pooling drops (19 -> 9).  Each
+// addend is the fp16 value the conv kernels' LM_POOL load yields; the sum of the two is rounded to fp16 once (v_pk_add_f16),
+// which is what Keras' Add layer does with two fp16 tensors under mixed_float16.
+__global__ __launch_bounds__(256) void add_pool_kernel(const f16 *__restrict__ za, const float *__restrict__ sca,
+                                                       const float *__restrict__ sha, const f16 *__restrict__ zb,
+                                                       const float *__restrict__ scb, const float *__restrict__ shb, int cs,
+                                                       int B, int H, int W, f16 *__restrict__ sum, int a_div) {
+    const int nc8 = cs / 8, Hh = H / 2, Wh = W / 2;
+    const long long n = (long long)B * Hh * Wh * nc8;
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int c0 = (int)(i % nc8) * 8;
+    const long long pix = i / nc8;
+    const int x = (int)(pix % Wh);
+    const long long r = pix / Wh;
+    const int y = (int)(r % Hh), b = (int)(r / Hh);
+    const size_t row = (size_t)W * cs;
+    f16x8 o[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int bz = s ? b : b / a_div;       // tower A: one image for a_div rows of the sum
+        const f16 *p = (s ? zb : za) + ((size_t)bz * H + 2 * y) * row + (size_t)(2 * x) * cs + c0;
+        const f16x8 v0 = *reinterpret_cast<const f16x8 *>(p), v1 = *reinterpret_cast<const f16x8 *>(p + cs);
+        const f16x8 v2 = *reinterpret_cast<const f16x8 *>(p + row), v3 = *reinterpret_cast<const f16x8 *>(p + row + cs);
+        o[s] = imk_affine_pool8(v0, v1, v2, v3, (s ? scb : sca) + c0, (s ? shb : sha) + c0);   // the LM_POOL load of the conv kernels
+    }
+    *reinterpret_cast<f16x8 *>(sum + (size_t)pix * cs + c0) = o[0] + o[1];
+}
+
 // class ids [n_pix] u8 -> fp16 one-hot [n_pix][cs] (what the reference's generator builds on the host, functions.py:4978)
 __global__ __launch_bounds__(256) void onehot_kernel(const uint8_t *__restrict__ cls, long long n_pix, int cs,
                                                      f16 *__restrict__ out) {
@@ -971,6 +1002,15 @@ int imk_launch_concat_pool(const f16 *za, const float *sca, const float *sha, in
     const long long n = (long long)B * Hh * Wh * ((csa + csb) / 8);
     imk_klaunch(concat_pool_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, stream, za, sca, sha, csa, zb, scb, shb, csb, B, Hh, Wh, cat,
                 a_div);
+    IMK_LAUNCH_CHECK();
+    return IMK_OK;
+}
+
+int imk_launch_add_pool(const f16 *za, const float *sca, const float *sha, const f16 *zb, const float *scb, const float *shb,
+                        int cs, int B, int H, int W, f16 *sum, hipStream_t stream, int a_div) {
+    IMK_CHECK_ARG(a_div >= 1 && B % a_div == 0 && cs > 0 && cs % 8 == 0 && H >= 2 && W >= 2);
+    const long long n = (long long)B * (H / 2) * (W / 2) * (cs / 8);
+    imk_klaunch(add_pool_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, stream, za, sca, sha, zb, scb, shb, cs, B, H, W, sum, a_div);
     IMK_LAUNCH_CHECK();
     return IMK_OK;
 }

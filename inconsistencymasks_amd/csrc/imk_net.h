@@ -93,7 +93,9 @@ struct Ws {
     size_t probs = 0, dlogit = 0, loss_partial = 0;
     size_t dice_partial = 0, dice_coef = 0, dice_val = 0;   // train, loss kind 4: per-image partial rows, (c0, c1) and Dice values
     // EvalNet
-    size_t cat = 0, dcat = 0;      // concatenated pooled tower outputs [B,H/2,W/2,2F] and their gradient
+    size_t cat = 0, dcat = 0;      // concatenated pooled tower outputs [B,H/2,W/2,2F] and their gradient (v2: their sum
+                                   // [B,H/16,W/16,ch[3]] and its gradient)
+    size_t dT[2][3] = {{0, 0, 0}, {0, 0, 0}};   // v2, train: gradient w.r.t. the pooled output of tower s's block j+1
     size_t onehot = 0;             // b_onehot: input B as fp16 one-hot [B,H,W,pad8(cb)]
     size_t head_partial = 0;       // train: per-sample Dense gradients and loss terms
     size_t sched = 0;              // inference (U-Net): IMK_SCHED_BYTES of tile counters per layer (ImkConvArgs::sched), zeroed per forward

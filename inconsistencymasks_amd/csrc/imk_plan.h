@@ -13,7 +13,7 @@ struct ImkLayer {
     int ksize, cin, cout;
     int64_t off_w, off_b;        // conv: kernel/bias; bn: gamma/beta (floats, trainable section)
     int64_t off_mean, off_var;   // bn (non-trainable section)
-    int res;       // resolution level of the layer's output: 0 = full ... 4 = 1/16
+    int res;       // resolution level of the layer's output: 0 = full ... 4 = 1/16 (EvalNet: to 6, its v2 Dense heads 7)
     // packed (fp16, MFMA fragment order) weights, byte offsets into the packed buffer
     int64_t pk_fwd, pk_bwd;      // conv only
     int64_t pk_bytes_fwd, pk_bytes_bwd;
@@ -40,6 +40,7 @@ struct imk_unet_plan {
     imk_unet_cfg cfg;            // EvalNet plans: h, w, c_in (= input A's channels), n_out and ch are filled too
     int net = 0;                 // 0 U-Net, 1 EvalNet
     imk_evalnet_cfg ecfg{};
+    int ev2 = 0;                 // EvalNet plans: 1 = get_evalnet_miou_v2 (four blocks per tower, add, three trunk blocks)
     std::vector<ImkLayer> layers;
     int64_t n_total, n_trainable;
     int64_t packed_bytes;

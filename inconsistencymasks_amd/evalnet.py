@@ -1,10 +1,12 @@
 """Host-side mirror of the reference's evalnet.py on top of libimk.so.
 
-`get_evalnet(i_height, i_width, inputA_channels, inputB_channels, alpha=2, ...)` (evalnet.py:24) and
-`get_evalnet_miou(...)` (evalnet.py:49) keep the reference signatures and return an `EvalNet` whose
-`.predict([A, B])` takes uint8 NHWC batches like `tf.keras.Model.predict` and returns what the Keras models return:
-one float32 [B,1] array, or the list [iou [B,Cb], detection [B,Cb]].  `get_evalnet_miou_v2` (evalnet.py:76, used by
-no shipped script) is not provided.  torch is used for device memory only.
+`get_evalnet(i_height, i_width, inputA_channels, inputB_channels, alpha=2, ...)` (evalnet.py:24),
+`get_evalnet_miou(...)` (evalnet.py:49) and `get_evalnet_miou_v2(...)` (evalnet.py:76) keep the reference signatures and
+return an `EvalNet` whose `.predict([A, B])` takes uint8 NHWC batches like `tf.keras.Model.predict` and returns what the
+Keras models return: one float32 [B,1] array, or the list [iou [B,Cb], detection [B,Cb]].  `get_evalnet_miou_v2` is the
+late-fusion network (four conv blocks per tower, add at 1/16 resolution, three trunk blocks; inputs from 128 x 128 up): no
+reference script calls it, but every EvalNet function here takes it, and `CandidateScorer` then runs the whole image tower
+once per image.  torch is used for device memory only.
 """
 import ctypes
 
@@ -20,14 +22,18 @@ class EvalPlan(Plan):
 
     _ws_fn = "imk_evalnet_workspace_bytes"
 
-    def __init__(self, h, w, ca, cb, n_out, alpha, two_heads, normalize_a, normalize_b, b_onehot=False):
-        ch = [int(v * alpha) for v in (16, 32, 64, 128, 256)]          # evalnet.py:28-41
+    def __init__(self, h, w, ca, cb, n_out, alpha, two_heads, normalize_a, normalize_b, b_onehot=False, arch="v1"):
+        if arch not in ("v1", "v2"):
+            raise ValueError(f"arch must be 'v1' or 'v2', got {arch!r}")
+        self.arch = arch                                               # "v2": get_evalnet_miou_v2 (evalnet.py:76-106)
+        ch = [int(v * alpha) for v in (16, 32, 64, 128, 256)]          # evalnet.py:28-41, 80-100
         self.cfg = EvalnetCfg(h, w, ca, cb, n_out, int(two_heads), int(normalize_a), int(normalize_b), (ctypes.c_int * 5)(*ch),
                               int(b_onehot))
         self.h, self.w, self.ca, self.cb, self.n_out, self.alpha = h, w, ca, cb, n_out, alpha
         self.two_heads, self.b_onehot = bool(two_heads), bool(b_onehot)
         self._p = ctypes.c_void_p()
-        check(lib.imk_evalnet_plan_create(ctypes.byref(self.cfg), ctypes.byref(self._p)), "imk_evalnet_plan_create")
+        create = "imk_evalnet_v2_plan_create" if arch == "v2" else "imk_evalnet_plan_create"
+        check(getattr(lib, create)(ctypes.byref(self.cfg), ctypes.byref(self._p)), create)
         self._describe()
 
 
@@ -35,8 +41,8 @@ class EvalNet(UNet):
     N_STATS = 8     # loss, overflow flag, loss scale, step, loss of head 0 (mse), loss of head 1 (bce), 2 spare
 
     def __init__(self, h, w, ca, cb, n_out, alpha, two_heads, normalize_a=True, normalize_b=True, seed=None, device="cuda",
-                 b_onehot=False):
-        self._init_from_plan(EvalPlan(h, w, ca, cb, n_out, alpha, two_heads, normalize_a, normalize_b, b_onehot), seed, device,
+                 b_onehot=False, arch="v1"):
+        self._init_from_plan(EvalPlan(h, w, ca, cb, n_out, alpha, two_heads, normalize_a, normalize_b, b_onehot, arch), seed, device,
                              dense=("dense", "iou", "detection"))
         self.n_heads = 2 if two_heads else 1
 
@@ -165,7 +171,8 @@ class CandidateScorer:
     def __init__(self, evalnets):
         self.models = list(evalnets)
         native = all(isinstance(m, EvalNet) for m in self.models)
-        self.shared = native and all(bytes(m.plan.cfg) == bytes(self.models[0].plan.cfg) for m in self.models)
+        self.shared = native and all(bytes(m.plan.cfg) == bytes(self.models[0].plan.cfg) and m.plan.arch == self.models[0].plan.arch
+                                     for m in self.models)
         self.n_heads = self.models[0].n_heads if native else None
         self._ws = {}
         if self.shared:
@@ -263,3 +270,16 @@ def get_evalnet_miou(i_height, i_width, inputA_channels, inputB_channels, alpha=
         raise NotImplementedError("a one-hot input is not divided by 255 in any reference script")
     return EvalNet(i_height, i_width, inputA_channels, inputB_channels, inputB_channels, alpha, True, normalize_A,
                    normalize_B, seed, device, b_onehot=onehot)
+
+
+def get_evalnet_miou_v2(i_height, i_width, inputA_channels, inputB_channels, alpha=2, actifu="relu", ksi=3,
+                        kernel_ini="he_normal", normalize_A=True, normalize_B=False, seed=None, device="cuda", onehot_B=None):
+    """evalnet.py:76 -- the late-fusion network: input block + four conv blocks per tower, add() of the towers at 1/16
+    resolution, three conv blocks, heads 'iou' and 'detection'.  Seven poolings: inputs from 128 x 128 up.  onehot_B as
+    get_evalnet_miou."""
+    _check_defaults(actifu, ksi, kernel_ini)
+    onehot = inputB_channels > 4 if onehot_B is None else bool(onehot_B)
+    if onehot and normalize_B:
+        raise NotImplementedError("a one-hot input is not divided by 255 in any reference script")
+    return EvalNet(i_height, i_width, inputA_channels, inputB_channels, inputB_channels, alpha, True, normalize_A,
+                   normalize_B, seed, device, b_onehot=onehot, arch="v2")

@@ -411,11 +411,14 @@ def save_evalnet(model, path):
     meta = {"net": "evalnet", "h": str(p.h), "w": str(p.w), "ca": str(p.ca), "cb": str(p.cb), "n_out": str(p.n_out),
             "alpha": repr(p.alpha), "two_heads": str(int(p.two_heads)), "normalize_a": str(p.cfg.normalize_a),
             "normalize_b": str(p.cfg.normalize_b), "b_onehot": str(int(p.b_onehot))}
+    if p.arch != "v1":          # get_evalnet_miou_v2; a v1 file stays byte for byte what it was
+        meta["arch"] = p.arch
     save_file({k: v.contiguous() for k, v in model.state_dict().items()}, path, metadata=meta)
 
 
 def load_evalnet(path, device="cuda"):
-    """load_model for an EvalNet file: this package's safetensors, or a Keras HDF5 checkpoint of evalnet.get_evalnet / get_evalnet_miou"""
+    """load_model for an EvalNet file: this package's safetensors, or a Keras HDF5 checkpoint of evalnet.get_evalnet / get_evalnet_miou /
+    get_evalnet_miou_v2"""
     from . import h5lite
     if h5lite.is_hdf5(path):
         from .keras_h5 import load_keras_evalnet
@@ -426,7 +429,7 @@ def load_evalnet(path, device="cuda"):
         sd = {k: f.get_tensor(k) for k in f.keys()}
     m = EvalNet(int(meta["h"]), int(meta["w"]), int(meta["ca"]), int(meta["cb"]), int(meta["n_out"]), float(meta["alpha"]),
                 bool(int(meta["two_heads"])), bool(int(meta["normalize_a"])), bool(int(meta["normalize_b"])), seed=0, device=device,
-                b_onehot=bool(int(meta.get("b_onehot", "0"))))
+                b_onehot=bool(int(meta.get("b_onehot", "0"))), arch=meta.get("arch", "v1"))
     m.load_state_dict(sd)
     return m
 

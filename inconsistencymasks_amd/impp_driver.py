@@ -17,7 +17,7 @@ import torch
 
 from . import functions as F
 from . import paths
-from .evalnet import get_evalnet, get_evalnet_miou
+from .evalnet import get_evalnet, get_evalnet_miou, get_evalnet_miou_v2
 from .im_driver import DATASETS, _ints, color_mapping, epoch_steps, train_candidates
 from .unet import get_unet
 
@@ -34,7 +34,18 @@ SCHEDULE = {"HeLa": _HELA, "ISIC_2018": _ISIC,
                                brb=[(-3, 3), (-6, 6), (-9, 9), (-12, 12), (-15, 15)])}
 
 
-def run(dataset, aug=False, train_new_evalnet=True, gt=False):
+def _miou_constructor(evalnet_arch, dataset):
+    """evalnet_arch "v1": get_evalnet_miou, what every reference script builds; "v2": get_evalnet_miou_v2 (evalnet.py:76), the late-fusion
+    network, in its place.  ISIC_2018's EvalNet is get_evalnet, of which the reference has no v2: refused by name."""
+    if evalnet_arch not in ("v1", "v2"):
+        raise ValueError(f"evalnet_arch must be 'v1' or 'v2', got {evalnet_arch!r}")
+    if evalnet_arch == "v2" and DATASETS[dataset]["kind"] == "isic":
+        raise ValueError(f"evalnet_arch='v2': {dataset} scores with get_evalnet, which has no v2 (get_evalnet_miou_v2 is the two-head network)")
+    return get_evalnet_miou_v2 if evalnet_arch == "v2" else get_evalnet_miou
+
+
+def run(dataset, aug=False, train_new_evalnet=True, gt=False, evalnet_arch="v1"):
+    miou_net = _miou_constructor(evalnet_arch, dataset)
     kind = DATASETS[dataset]["kind"]            # isic | hela | multi
     hela, multi = kind == "hela", kind == "multi"
     tag = {"HeLa": "HELA", "ISIC_2018": "ISIC_2018", "SUIM": "SUIM", "Cityscapes": "CITYSCAPES"}[dataset]
@@ -86,9 +97,9 @@ def run(dataset, aug=False, train_new_evalnet=True, gt=False):
                 name = f"{evalnet_tag}_{runid}_{i}"
                 h5 = os.path.join(model_dir, name + ".h5")
                 if hela:
-                    evalnet = get_evalnet_miou(H, W, C, K, alpha_evalnet, seed=7000 * runid + i)
+                    evalnet = miou_net(H, W, C, K, alpha_evalnet, seed=7000 * runid + i)
                 elif multi:
-                    evalnet = get_evalnet_miou(H, W, C, K, alpha_evalnet, seed=7000 * runid + i, onehot_B=True)
+                    evalnet = miou_net(H, W, C, K, alpha_evalnet, seed=7000 * runid + i, onehot_B=True)
                 else:
                     evalnet = get_evalnet(H, W, C, K, alpha_evalnet, normalize_B=True, seed=7000 * runid + i)
                 if side_by_side:      # no side stream of its own: the other candidates fill the gaps (results identical)

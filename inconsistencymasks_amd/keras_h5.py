@@ -243,12 +243,25 @@ def save_keras_weights(model_or_sd, path, c_in=None, n_out=None, alpha=None, own
 
 
 # ---------------------------------------------------------------------------------------------------------------- EvalNet (evalnet.py:24-73)
-def evalnet_layer_table(ca, cb, n_out, alpha, two_heads):
+def evalnet_layer_table(ca, cb, n_out, alpha, two_heads, arch="v1"):
     """(name, kind, k, cin, cout) in evalnet.py's creation order -- the order of the plan's flat parameter vector: tower A (input block,
-    conv block), tower B, five merged blocks, the Dense head(s) as 1x1 'convs' on the pooled features"""
+    conv block), tower B, five merged blocks, the Dense head(s) as 1x1 'convs' on the pooled features.  arch "v2"
+    (get_evalnet_miou_v2, evalnet.py:76-106): input block + four conv blocks per tower, three merged blocks, the two heads"""
     f = lambda v: int(v * alpha)
     f0 = f(16)
     t = []
+    if arch == "v2":
+        block = lambda n, ci, co: [(f"{n}.c3", "conv", 3, ci, co), (f"{n}.c1", "conv", 1, co, co), (f"{n}.bn", "bn", 0, co, co)]
+        for tw, cin in (("a", ca), ("b", cb)):
+            t += [(f"{tw}.in.c", "conv", 1, cin, f0), (f"{tw}.in.bn", "bn", 0, f0, f0)]
+            prev = f0
+            for j, v in enumerate((16, 32, 64, 128), start=1):
+                t += block(f"{tw}{j}", prev, f(v))
+                prev = f(v)
+        for i, v in enumerate((64, 128, 256), start=1):
+            t += block(f"m{i}", prev, f(v))
+            prev = f(v)
+        return t + [("iou", "conv", 1, prev, n_out), ("detection", "conv", 1, prev, n_out)]
     for tw, cin in (("a", ca), ("b", cb)):
         t += [(f"{tw}.in.c", "conv", 1, cin, f0), (f"{tw}.in.bn", "bn", 0, f0, f0),
               (f"{tw}.c3", "conv", 3, f0, f0), (f"{tw}.c1", "conv", 1, f0, f0), (f"{tw}.bn", "bn", 0, f0, f0)]
@@ -283,14 +296,16 @@ def evalnet_state_dict_from_keras_h5(path):
     bns = sorted([n for n in weights_of if re.fullmatch(r"batch_normalization(_\d+)?", n)], key=_suffix)
     two = "iou" in weights_of and "detection" in weights_of
     dense = [n for n in weights_of if re.fullmatch(r"dense(_\d+)?", n)]
-    if len(convs) != 16 or len(bns) != 9 or not (two or len(dense) == 1):
-        raise ValueError(f"{path}: not an evalnet.get_evalnet / get_evalnet_miou checkpoint ({len(convs)} Conv2D, {len(bns)} BatchNormalization, "
-                         f"heads {sorted(set(weights_of) - set(convs) - set(bns))})")
-    k_a, k_b = weights_of[convs[0]]["kernel"], weights_of[convs[3]]["kernel"]
+    # get_evalnet_miou_v2: 24 Conv2D (9 per tower, 6 in the trunk), 13 BatchNormalization, the two named Dense heads
+    arch = "v2" if (len(convs), len(bns)) == (24, 13) and two else "v1"
+    if arch == "v1" and (len(convs) != 16 or len(bns) != 9 or not (two or len(dense) == 1)):
+        raise ValueError(f"{path}: not an evalnet.get_evalnet / get_evalnet_miou / get_evalnet_miou_v2 checkpoint ({len(convs)} Conv2D, "
+                         f"{len(bns)} BatchNormalization, heads {sorted(set(weights_of) - set(convs) - set(bns))})")
+    k_a, k_b = weights_of[convs[0]]["kernel"], weights_of[convs[9 if arch == "v2" else 3]]["kernel"]
     head = weights_of["iou" if two else dense[0]]["kernel"]
     ca, cb, n_out = int(k_a.shape[2]), int(k_b.shape[2]), int(head.shape[-1])
     _, _, alpha = infer_config(k_a.shape, (1, 1, 1, 1))
-    table = evalnet_layer_table(ca, cb, n_out, alpha, two)
+    table = evalnet_layer_table(ca, cb, n_out, alpha, two, arch)
     it_c, it_b = iter(convs), iter(bns)
     sd = {}
     for name, kind, k, ci, co in table:
@@ -309,6 +324,8 @@ def evalnet_state_dict_from_keras_h5(path):
             for ours, theirs in (("gamma", "gamma"), ("beta", "beta"), ("mean", "moving_mean"), ("var", "moving_variance")):
                 sd[f"{name}.{ours}"] = np.asarray(w[theirs], np.float32)
     meta = {"h": None, "w": None, "ca": ca, "cb": cb, "n_out": n_out, "alpha": alpha, "two_heads": two, "normalize_a": None, "normalize_b": None}
+    if arch != "v1":          # a v1 file's record stays what it was
+        meta["arch"] = arch
     layers = _config_layers(cfg)
     if layers:
         # the two Inputs in model_config["config"]["input_layers"] order (A first, evalnet.py:45); a Lambda fed by an input = its x / 255
@@ -340,7 +357,7 @@ def load_keras_evalnet(path, height=None, width=None, normalize_a=None, normaliz
         raise ValueError(f"{path}: a weights-only HDF5 file does not record the input size / which inputs are divided by 255 -- pass "
                          "height=, width=, normalize_a=, normalize_b=")
     net = EvalNet(int(h), int(w), m["ca"], m["cb"], m["n_out"], m["alpha"], m["two_heads"], bool(na), bool(nb), seed=0, device=device,
-                  b_onehot=bool(m.get("b_onehot", False)))
+                  b_onehot=bool(m.get("b_onehot", False)), arch=m.get("arch", "v1"))
     net.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in sd.items()})
     return net
 
@@ -349,12 +366,15 @@ def save_keras_evalnet_weights(model, path):
     """The EvalNet's weights in the layout of Keras' save_weights (HDF5); Dense kernels as [features, units]."""
     p = model.plan
     sd = {k: v.numpy() for k, v in model.state_dict().items()}
-    table = evalnet_layer_table(p.ca, p.cb, p.n_out, p.alpha, p.two_heads)
+    table = evalnet_layer_table(p.ca, p.cb, p.n_out, p.alpha, p.two_heads, p.arch)
     kn = evalnet_keras_layer_names(table)
     tree = {}
     # `layer_names` in the order of Keras' model.layers for this graph (layers by depth, creation order inside a depth): the two towers
     # interleave -- the order load_weights(by_name=False) zips with; by_name=True does not depend on it
-    towers = [f"{t}.{l}" for l in ("in.c", "in.bn", "c3", "c1", "bn") for t in ("a", "b")]
+    if p.arch == "v2":
+        towers = [f"{t}{l}" for l in [".in.c", ".in.bn"] + [f"{j}.{q}" for j in (1, 2, 3, 4) for q in ("c3", "c1", "bn")] for t in ("a", "b")]
+    else:
+        towers = [f"{t}.{l}" for l in ("in.c", "in.bn", "c3", "c1", "bn") for t in ("a", "b")]
     order = [kn[n].encode() for n in towers + [n for n, *_ in table if n not in towers]]
     for name, kind, k, ci, co in table:
         kname = kn[name]
@@ -368,5 +388,7 @@ def save_keras_evalnet_weights(model, path):
                        kname: {w: np.asarray(a, np.float32) for w, a in ws.items()}}
     own = {"net": "evalnet", "h": p.h, "w": p.w, "ca": p.ca, "cb": p.cb, "n_out": p.n_out, "alpha": p.alpha, "two_heads": bool(p.two_heads),
            "normalize_a": bool(p.cfg.normalize_a), "normalize_b": bool(p.cfg.normalize_b), "b_onehot": bool(p.b_onehot)}
+    if p.arch != "v1":          # the layer counts say it as well; a v1 file stays byte for byte what it was
+        own["arch"] = p.arch
     tree[h5lite.ATTRS] = {"layer_names": order, "backend": b"tensorflow", "keras_version": b"2.10.0", "imk_config": json.dumps(own)}
     h5lite.write(path, tree)

@@ -25,7 +25,7 @@ import torch
 
 from . import functions as F
 from . import paths
-from .evalnet import get_evalnet, get_evalnet_miou
+from .evalnet import get_evalnet, get_evalnet_miou, get_evalnet_miou_v2
 from .im_driver import DATASETS, NOISY_STUDENT_HELA_HEADER, _ints, color_mapping, epoch_steps, train_candidates
 from .unet import get_unet
 
@@ -68,9 +68,20 @@ def single_names(dataset):
     return dataset, f"{dataset}_evalnet_miou", "evalnet", f"{dataset}_segnet_miou"
 
 
-def run(dataset, train_new_evalnet=True, ensemble=True):
+def _miou_constructor(evalnet_arch, dataset):
+    """evalnet_arch "v1": get_evalnet_miou, what every reference script builds; "v2": get_evalnet_miou_v2 (evalnet.py:76), the late-fusion
+    network, in its place.  ISIC_2018's EvalNet is get_evalnet, of which the reference has no v2: refused by name."""
+    if evalnet_arch not in ("v1", "v2"):
+        raise ValueError(f"evalnet_arch must be 'v1' or 'v2', got {evalnet_arch!r}")
+    if evalnet_arch == "v2" and DATASETS[dataset]["kind"] == "isic":
+        raise ValueError(f"evalnet_arch='v2': {dataset} scores with get_evalnet, which has no v2 (get_evalnet_miou_v2 is the two-head network)")
+    return get_evalnet_miou_v2 if evalnet_arch == "v2" else get_evalnet_miou
+
+
+def run(dataset, train_new_evalnet=True, ensemble=True, evalnet_arch="v1"):
+    miou_net = _miou_constructor(evalnet_arch, dataset)
     if not ensemble:
-        return _run_single(dataset, train_new_evalnet)
+        return _run_single(dataset, train_new_evalnet, miou_net)
     kind = DATASETS[dataset]["kind"]            # isic | hela | multi
     hela, multi = kind == "hela", kind == "multi"
     tag, evalnet_tag, ev_sub, segnet_tag = names(dataset)
@@ -116,9 +127,9 @@ def run(dataset, train_new_evalnet=True, ensemble=True):
                 name = f"{evalnet_tag}_{runid}_{i}"
                 h5 = os.path.join(model_dir, name + ".h5")
                 if hela:
-                    evalnet = get_evalnet_miou(H, W, C, K, alpha_evalnet, seed=9000 * runid + i)
+                    evalnet = miou_net(H, W, C, K, alpha_evalnet, seed=9000 * runid + i)
                 elif multi:
-                    evalnet = get_evalnet_miou(H, W, C, K, alpha_evalnet, seed=9000 * runid + i, onehot_B=True)
+                    evalnet = miou_net(H, W, C, K, alpha_evalnet, seed=9000 * runid + i, onehot_B=True)
                 else:
                     evalnet = get_evalnet(H, W, C, K, alpha_evalnet, normalize_B=True, seed=9000 * runid + i)
                 if side_by_side:      # no side stream of its own: the other candidates fill the gaps (results identical)
@@ -213,7 +224,7 @@ def run(dataset, train_new_evalnet=True, ensemble=True):
                 barrier()
 
 
-def _run_single(dataset, train_new_evalnet=True):
+def _run_single(dataset, train_new_evalnet=True, miou_net=None):
     """the single-EvalNet loop (module docstring)"""
     tag, evalnet_tag, ev_sub, segnet_tag = single_names(dataset)
     multi = DATASETS[dataset]["kind"] == "multi"
@@ -255,7 +266,7 @@ def _run_single(dataset, train_new_evalnet=True):
                         model_i += 1
                         del model
             if multi:
-                evalnet = get_evalnet_miou(H, W, C, K, alpha_evalnet, seed=9000 * runid, onehot_B=True)
+                evalnet = (miou_net or get_evalnet_miou)(H, W, C, K, alpha_evalnet, seed=9000 * runid, onehot_B=True)
                 res = F.train_evalnet_miou_model_multiclass(evalnet, H, W, tr, va, evalnet_h5, bs_evalnet, K, ep_evalnet)
                 row = list(res)      # total_loss, iou_loss, conf_loss, iou_mae, conf_mae under the three-name header, as the script writes it
             else:
