@@ -483,6 +483,18 @@ IMK_API int imk_eval_soft_sums(const float *probs, const uint8_t *gt, int64_t n_
  * validation images. */
 IMK_API int imk_eval_dice_sums(const float *probs, const uint8_t *gt, int batch, int h, int w, int k, double *out, void *stream);
 
+/* The label of the scalar-IoU multiclass EvalNet family (csrc/imk_label.hip): the writers' `image[im > 0] = 0; pred[im > 0] = 0`
+ * and the per-class pixel counts get_IoU_multi_unique (functions.py:1791-1816) is a ratio of, in one pass.
+ *   pred, gt [B,H,W] u8 class ids 0..255; im [B,H,W] u8 or NULL: a pixel with im > 0 is blocked -- its prediction counts as class 0,
+ *   pred_blocked [B,H,W] u8 (may be NULL, may alias pred) stores p' = the blocked prediction, image [B,H,W,c] u8 (may be NULL;
+ *   c = 1 or 3) is zeroed there in place: the bytes imk_block_apply and a copy leave.
+ *   counts [B,4,256] int64: [0][v] = #(gt == v), [1][v] = #(p' == v), [2][v] = #(gt == v & p' == v), [3][v] = #(gt == v & im == 0)
+ *   (im NULL: row 3 = row 0).  Zeroed by the call on `stream`; integer arithmetic only, so the result does not depend on the grid.
+ * Asynchronous, allocates nothing.  IMK_EINVAL (before any launch): a NULL pred / gt / counts, non-positive sizes, image given with
+ * c other than 1 or 3.  IMK_EUNSUPPORTED: h * w >= 2^31, batch > 65535. */
+IMK_API int imk_label_counts(const uint8_t *pred, const uint8_t *gt, const uint8_t *im, uint8_t *image, int c, int batch, int h, int w,
+                     uint8_t *pred_blocked, int64_t *counts, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Depth-map (regression) family (csrc/imk_depth.hip): get_im_prediction_depth_map (functions.py:6155-6177), benchmark_depth_map
  * (:1345-1384), rmse / delta_metric (:36-48)

@@ -85,7 +85,7 @@ int imk_launch_concat_pool(const f16 *za, const float *sca, const float *sha, in
 // the towers' last Conv1x1 outputs (the sum is H/2 x W/2, an odd last row / column dropped); a_div as above
 int imk_launch_add_pool(const f16 *za, const float *sca, const float *sha, const f16 *zb, const float *scb, const float *shb,
                         int cs, int B, int H, int W, f16 *sum, hipStream_t stream, int a_div = 1);
-int imk_launch_onehot(const uint8_t *cls, long long n_pix, int cs, f16 *out, hipStream_t stream);
+int imk_launch_onehot(const uint8_t *cls, long long n_pix, int cs, bool div255, f16 *out, hipStream_t stream);
 size_t imk_evalnet_head_partial_floats(int B, int n_heads, int K, int C);
 int imk_launch_evalnet_head(const f16 *z, const float *sc, const float *sh, const float *const *w, const float *const *bias,
                             int n_heads, int K, int C, int cs, int B, int H, int W, float *out, const float *y,

@@ -627,8 +627,10 @@ __global__ __launch_bounds__(256) void add_pool_kernel(const f16 *__restrict__ z
     *reinterpret_cast<f16x8 *>(sum + (size_t)pix * cs + c0) = o[0] + o[1];
 }
 
-// class ids [n_pix] u8 -> fp16 one-hot [n_pix][cs] (what the reference's generator builds on the host, functions.py:4978)
-__global__ __launch_bounds__(256) void onehot_kernel(const uint8_t *__restrict__ cls, long long n_pix, int cs,
+// class ids [n_pix] u8 -> fp16 one-hot [n_pix][cs] (what the reference's generator builds on the host, functions.py:4978).
+// `on`: the value of the hot channel -- 1, or under the x / 255 Lambda (get_evalnet's normalize_B) what the normalised uint8 stem
+// forms for the byte 1 (imk_launch_onehot)
+__global__ __launch_bounds__(256) void onehot_kernel(const uint8_t *__restrict__ cls, long long n_pix, int cs, f16 on,
                                                      f16 *__restrict__ out) {
     const int nc8 = cs / 8;
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -637,7 +639,7 @@ __global__ __launch_bounds__(256) void onehot_kernel(const uint8_t *__restrict__
     const int c0 = (int)(i - pix * nc8) * 8, k = cls[pix];
     f16x8 o;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (f16)(c0 + j == k ? 1.0f : 0.0f);
+    for (int j = 0; j < 8; ++j) o[j] = c0 + j == k ? on : (f16)0.0f;
     *reinterpret_cast<f16x8 *>(out + pix * cs + c0) = o;
 }
 
@@ -1015,9 +1017,11 @@ int imk_launch_add_pool(const f16 *za, const float *sca, const float *sha, const
     return IMK_OK;
 }
 
-int imk_launch_onehot(const uint8_t *cls, long long n_pix, int cs, f16 *out, hipStream_t stream) {
+int imk_launch_onehot(const uint8_t *cls, long long n_pix, int cs, bool div255, f16 *out, hipStream_t stream) {
+    // the uint8 stem's own expression for x / 255 (imk_stage.h): fp16(1 * (1 / 255)), which is fp16(1 / 255) correctly rounded
+    const f16 on = div255 ? (f16)(1.0f * (1.0f / 255.0f)) : (f16)1.0f;
     const long long n = n_pix * (cs / 8);
-    imk_klaunch(onehot_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, stream, cls, n_pix, cs, out);
+    imk_klaunch(onehot_kernel, dim3((int)((n + 255) / 256)), dim3(256), 0, stream, cls, n_pix, cs, on, out);
     IMK_LAUNCH_CHECK();
     return IMK_OK;
 }

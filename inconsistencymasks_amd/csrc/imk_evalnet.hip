@@ -193,7 +193,7 @@ int run_forward(Ctx &c, const ETopo &t, float *params_rw, int a_div = 1) {
 #define OK(e) do { rc = (e); if (rc) return rc; } while (0)
     const imk_evalnet_cfg &e = c.p->ecfg;
     if (e.b_onehot)
-        OK(imk_launch_onehot(c.x_in[1], (long long)c.B * e.h * e.w, imk_pad8(e.cb), reinterpret_cast<f16 *>(c.base + c.ws.onehot),
+        OK(imk_launch_onehot(c.x_in[1], (long long)c.B * e.h * e.w, imk_pad8(e.cb), e.normalize_b != 0, reinterpret_cast<f16 *>(c.base + c.ws.onehot),
                              c.stream));
     const int B_rows = c.B;
     if (c.p->ev2) {   // all of tower A (input block + four blocks) at batch B_rows / a_div; tower B and the trunk at B_rows

@@ -253,10 +253,15 @@ def _check_defaults(actifu, ksi, kernel_ini):
 
 
 def get_evalnet(i_height, i_width, inputA_channels, inputB_channels, alpha=2, actifu="relu", ksi=3, kernel_ini="he_normal",
-                normalize_A=True, normalize_B=True, seed=None, device="cuda"):
-    """evalnet.py:24 -- one sigmoid unit."""
+                normalize_A=True, normalize_B=True, seed=None, device="cuda", onehot_B=None):
+    """evalnet.py:24 -- one sigmoid unit.  onehot_B as get_evalnet_miou: input B is the one-hot stack of a class-id map (the scalar-IoU
+    multiclass scripts, functions.py:5217), passed as class ids and expanded on the device; default True when inputB_channels > 4.
+    With normalize_B (this constructor's default) the stack goes through the x / 255 Lambda like any input: the hot channel then
+    holds the fp16 value the normalised uint8 stem forms for the byte 1."""
     _check_defaults(actifu, ksi, kernel_ini)
-    return EvalNet(i_height, i_width, inputA_channels, inputB_channels, 1, alpha, False, normalize_A, normalize_B, seed, device)
+    onehot = inputB_channels > 4 if onehot_B is None else bool(onehot_B)
+    return EvalNet(i_height, i_width, inputA_channels, inputB_channels, 1, alpha, False, normalize_A, normalize_B, seed, device,
+                   b_onehot=onehot)
 
 
 def get_evalnet_miou(i_height, i_width, inputA_channels, inputB_channels, alpha=2, actifu="relu", ksi=3,

@@ -501,14 +501,8 @@ def _load_binary_evalnet_set(main_path, pool):
             torch.tensor([[r[1]] for r in rows], dtype=torch.float32, device="cuda"))
 
 
-def train_evalnet_ISIC_2018(model, train_main_path, val_main_path, filepath_h5, batch_size, epochs, seed=None):
-    """functions.py:4464-4506: loss 'mean_squared_error', metric 'mean_absolute_error', best epoch by
-    val_mean_absolute_error (min).  Returns (mse, mae) of the best model on the validation generator."""
-    F = _F()
-    with F._pool() as pool:
-        tr = _cached_evalnet_set("binary", train_main_path, lambda: _load_binary_evalnet_set(train_main_path, pool))
-        va = _cached_evalnet_set("binary", val_main_path, lambda: _load_binary_evalnet_set(val_main_path, pool))
-
+def _mse_mae_evaluator(batch_size):
+    """model.evaluate of a one-unit EvalNet compiled with loss 'mean_squared_error', metrics ['mean_absolute_error'] -> (mse, mae)"""
     def ev(m, st, steps):
         rows = []
         for s in range(steps):
@@ -519,8 +513,17 @@ def train_evalnet_ISIC_2018(model, train_main_path, val_main_path, filepath_h5, 
         for r in (torch.stack(rows).cpu().numpy() if rows else []):      # one transfer; summed on the host in batch order
             tot += r
         return tuple(tot / max(steps, 1))
+    return ev
 
-    return _fit_evalnet(model, tr, va, filepath_h5, batch_size, epochs, ev, 1, seed)
+
+def train_evalnet_ISIC_2018(model, train_main_path, val_main_path, filepath_h5, batch_size, epochs, seed=None):
+    """functions.py:4464-4506: loss 'mean_squared_error', metric 'mean_absolute_error', best epoch by
+    val_mean_absolute_error (min).  Returns (mse, mae) of the best model on the validation generator."""
+    F = _F()
+    with F._pool() as pool:
+        tr = _cached_evalnet_set("binary", train_main_path, lambda: _load_binary_evalnet_set(train_main_path, pool))
+        va = _cached_evalnet_set("binary", val_main_path, lambda: _load_binary_evalnet_set(val_main_path, pool))
+    return _fit_evalnet(model, tr, va, filepath_h5, batch_size, epochs, _mse_mae_evaluator(batch_size), 1, seed)
 
 
 def _load_multiclass_evalnet_set(main_path, num_classes, pool):
@@ -639,19 +642,9 @@ def create_augment_images_and_masks_with_evalnet_ensemble_binary(evalnets, h, w,
             m = torch.from_numpy(F.read_png_stack(pool, [os.path.join(min_, n) for n in chunk], 1)).cuda()
             xin = x.flip(-1).contiguous() if flip else x
             mean_iou = torch.stack([e.predict_device(xin, m) for e in evalnets], 0).double().mean(0)[:, 0].cpu().numpy()
-            n_augs = torch.tensor([num_augs_from_miou(v, min_threshold, max_threshold) for v in mean_iou], device="cuda")
-            jobs = []
-            for j in range(5):
-                sel = torch.nonzero(n_augs > j).flatten()
-                if not sel.numel():
-                    break
-                o, om = augment_batch(x[sel].contiguous(), m[sel].contiguous(), draw_params(int(sel.numel()), **draw_kw))
-                o, om = o.cpu().numpy(), om.cpu().numpy()
-                for row, i in enumerate(sel.tolist()):
-                    name = f"{chunk[i][:-4]}___{j}.png"
-                    jobs.append((os.path.join(iout, name), o[row]))
-                    jobs.append((os.path.join(mout, name), om[row, :, :, 0]))
-            F.write_pngs_async(jobs)      # on the writer pool: the next batch's decode, network pass and augmentation run meanwhile
+            n_augs = [num_augs_from_miou(v, min_threshold, max_threshold) for v in mean_iou]
+            # on the writer pool: the next batch's decode, network pass and augmentation run meanwhile
+            F.write_pngs_async(_write_augmented(chunk, x, m, n_augs, draw_kw, iout, mout))
     F.flush_writes()
     if F._dist():
         F._dist().barrier()
@@ -683,19 +676,8 @@ def create_augment_images_and_masks_with_gt(main_gt_input_path, min_threshold, m
                 gt[im_np[i, :, :, 0] > 0] = 0                                  # :6102
                 n_augs.append(num_augs_from_miou(F.get_IoU_multi_unique(m_np[i, :, :, 0], gt), min_threshold, max_threshold))
             x, m = torch.from_numpy(x_np).cuda(), torch.from_numpy(m_np).cuda()
-            n_augs = torch.tensor(n_augs, device="cuda")
-            jobs = []
-            for j in range(5):
-                sel = torch.nonzero(n_augs > j).flatten()
-                if not sel.numel():
-                    break
-                o, om = augment_batch(x[sel].contiguous(), m[sel].contiguous(), draw_params(int(sel.numel()), **draw_kw))
-                o, om = o.cpu().numpy(), om.cpu().numpy()
-                for row, i in enumerate(sel.tolist()):
-                    name = f"{chunk[i][:-4]}___{j}.png"
-                    jobs.append((os.path.join(iout, name), o[row]))
-                    jobs.append((os.path.join(mout, name), om[row, :, :, 0]))
-            F.write_pngs_async(jobs)      # on the writer pool: the next batch's decode, network pass and augmentation run meanwhile
+            # on the writer pool: the next batch's decode, network pass and augmentation run meanwhile
+            F.write_pngs_async(_write_augmented(chunk, x, m, n_augs, draw_kw, iout, mout))
     F.flush_writes()
     if F._dist():
         F._dist().barrier()
@@ -728,19 +710,8 @@ def create_augment_images_and_masks_with_evalnet_ensemble_multiclass(evalnets, h
             for row in outs:
                 valid = [row[ci] for ci in range(1, num_classes) if row[num_classes + ci] >= 0.5]
                 n_augs.append(num_augs_from_miou(sum(valid) / len(valid) if valid else 0.0, min_threshold, max_threshold))
-            n_augs = torch.tensor(n_augs, device="cuda")
-            jobs = []
-            for j in range(5):
-                sel = torch.nonzero(n_augs > j).flatten()
-                if not sel.numel():
-                    break
-                o, om = augment_batch(x[sel].contiguous(), m[sel].contiguous(), draw_params(int(sel.numel()), **draw_kw))
-                o, om = o.cpu().numpy(), om.cpu().numpy()
-                for row, i in enumerate(sel.tolist()):
-                    name = f"{chunk[i][:-4]}___{j}.png"
-                    jobs.append((os.path.join(iout, name), o[row]))
-                    jobs.append((os.path.join(mout, name), om[row, :, :, 0]))
-            F.write_pngs_async(jobs)      # on the writer pool: the next batch's decode, network pass and augmentation run meanwhile
+            # on the writer pool: the next batch's decode, network pass and augmentation run meanwhile
+            F.write_pngs_async(_write_augmented(chunk, x, m, n_augs, draw_kw, iout, mout))
     F.flush_writes()
     if F._dist():
         F._dist().barrier()
@@ -1081,3 +1052,252 @@ def create_training_data_evalnet_miou_multiclass(model, h, w, c, num_classes, im
             shutil.copy(os.path.join(images_path, n), os.path.join(iout, n))
             shutil.copy(os.path.join(masks_path, n), os.path.join(mout, n))
     _append_labels(main_output_path, rows)
+
+
+# ---------------------------------------------------------------------------------------------------
+# the scalar-IoU multiclass EvalNet family (functions.py:3496-3567, 3673-3769, 4509-4552, 5158-5317, 5762-5831; the SUIM / Cityscapes
+# twin of the ISIC chain): get_evalnet with the one-hot class stack as input B and one sigmoid unit, trained on the mean IoU over the
+# classes of a prediction.  Every label is get_IoU_multi_unique(ground truth, prediction) -- the ground truth in the `pred` seat, so the
+# classes that count are the PREDICTION's, class 0 included as soon as an IM pixel is blocked -- formed on the host from the integer
+# counts of imk_label_counts (evaluate.label_counts / iou_multi_unique_from_counts).
+# ---------------------------------------------------------------------------------------------------
+def compute_classwise_confluence(gt, num_classes):
+    """functions.py:4360-4379: the share of the pixels each class covers, rounded to 4 decimals"""
+    gt = np.asarray(gt)
+    total_pixels = gt.size
+    confluence_list = [0] * num_classes
+    for cls in range(num_classes):
+        confluence_list[cls] = round((gt == cls).sum() / total_pixels, 4)
+    return confluence_list
+
+
+def get_confluence_binary(gt):
+    """functions.py:4381-4395: sum of the mask over its size, rounded to 4 decimals (a 0 / 1 mask: the foreground share)"""
+    gt = np.asarray(gt)
+    return round(gt.sum() / gt.size, 4)
+
+
+def _class_probs(model, x):
+    """a segmentation model's probabilities [B,H,W,K] f32 on the device: a native U-Net, or anything with Keras' .predict"""
+    if hasattr(model, "predict_device"):
+        return model.predict_device(x)
+    return torch.from_numpy(np.ascontiguousarray(np.asarray(model.predict(x.cpu().numpy()), dtype=np.float32))).cuda()
+
+
+def _one_hot_u8(ids, num_classes):
+    """class ids u8 [...,1] or [...] -> the 0 / 1 stack u8 [...,K] (functions.py:5217: a value >= num_classes has no hot channel)"""
+    ids = ids[..., 0] if ids.shape[-1] == 1 and ids.dim() > 3 else ids
+    return (ids[..., None] == torch.arange(num_classes, device=ids.device, dtype=ids.dtype)).to(torch.uint8)
+
+
+def create_training_data_evalnet_multiclass(model, h, w, c, images_path, masks_path, main_output_path, i, rgb=True):
+    """functions.py:3496-3567: masks/<stem>___{i}.png = the arg-max class ids of every labelled image, with the mean IoU over the
+    prediction's classes against the ground truth (rounded to 4 decimals as numpy rounds a float64) appended to labels.csv; for
+    i == 0 also the labelled pairs themselves with the label 1.0."""
+    from . import evaluate as _ev
+    F = _F()
+    iout, mout = os.path.join(main_output_path, "images"), os.path.join(main_output_path, "masks")
+    os.makedirs(iout, exist_ok=True)
+    os.makedirs(mout, exist_ok=True)
+    mine = F.shard_list(os.listdir(images_path))
+    rows = []
+    with F._pool() as pool:
+        for s in range(0, len(mine), 64):
+            chunk = mine[s:s + 64]
+            x = torch.from_numpy(F.read_png_stack(pool, [os.path.join(images_path, n) for n in chunk], c)).cuda()
+            g = torch.from_numpy(F.read_png_stack(pool, [os.path.join(masks_path, n) for n in chunk], 1)).cuda()[..., 0].contiguous()
+            if (not rgb) and c == 3:
+                x = x.flip(-1).contiguous()
+            pred = _ev.eval_multiclass(_class_probs(model, x), g, want_pred=True)[0]      # np.argmax's rule
+            counts = _ev.label_counts(pred, g)[1]
+            pred = pred.cpu().numpy()
+            jobs = []
+            for j, n in enumerate(chunk):
+                jobs.append((os.path.join(mout, _pred_name(n, i)), pred[j]))
+                rows.append((_pred_name(n, i), round(_ev.iou_multi_unique_from_counts(counts[j], "pred"), 4)))
+            F.write_pngs_async(jobs)
+    F.flush_writes()
+    if i == 0:
+        for n in mine:
+            rows.append((n, 1.0))
+            shutil.copy(os.path.join(images_path, n), os.path.join(iout, n))
+            shutil.copy(os.path.join(masks_path, n), os.path.join(mout, n))
+    _append_labels(main_output_path, rows)
+
+
+def create_training_data_evalnet_im_multiclass(models, h, w, c, images_path, masks_path, main_output_path, num_loops, n_min_models=2,
+                                               n_max_models=4, rgb=True, brightness_range_alpha=(0.6, 1.4),
+                                               brightness_range_beta=(-20, 20), max_blur=3, max_noise=20, free_rotation=False,
+                                               seed=None):
+    """functions.py:3673-3769.  Per loop and labelled image: a random sub-ensemble -> argmax agreement IM, randomly eroded / dilated
+    -> blocked image + label map, label = the mean IoU over the blocked prediction's classes against the ground truth (rounded to 4
+    decimals); half of the samples are written augmented.  Blocking (image and label map) and the label counts of a chunk are ONE
+    imk_label_counts call.  `{stem}_aug_{loop}.png`, labels.csv."""
+    from . import evaluate as _ev
+    F = _F()
+    flip = (not rgb) and c == 3      # rgb=False (functions.py:3611 ff.): the nets see the file's channels in OpenCV's order (BGR)
+    rng = random.Random(F.SEED if seed is None else seed)
+    np_rng = np.random.default_rng(rng.getrandbits(32))
+    iout, mout = os.path.join(main_output_path, "images"), os.path.join(main_output_path, "masks")
+    os.makedirs(iout, exist_ok=True)
+    os.makedirs(mout, exist_ok=True)
+    names = sorted(os.listdir(images_path))
+    draw_kw = dict(brightness_range_alpha=brightness_range_alpha, brightness_range_beta=brightness_range_beta,
+                   max_blur=max_blur, max_noise=max_noise, free_rotation=free_rotation, rng=rng, np_rng=np_rng)
+    rows, stage = [], _LoopIM(models, POOLED)
+    with F._pool() as pool:
+        for nl in range(num_loops):
+            plan = _draw_plan(rng, len(names), len(models), n_min_models, n_max_models)
+            prm = _draw_aug(plan, F.INFER_BATCH, draw_kw)
+            loop_rows = {}
+            for subset, idx in _chunks(plan, F.INFER_BATCH, stage.pooled):
+                x = torch.from_numpy(F.read_png_stack(pool, [os.path.join(images_path, names[i]) for i in idx], c)).cuda()
+                gt = torch.from_numpy(F.read_png_stack(pool, [os.path.join(masks_path, names[i]) for i in idx], 1)).cuda()[..., 0].contiguous()
+                r, im = stage.run(plan, subset, idx, x.flip(-1).contiguous() if flip else x, F.THRESHOLD, False)
+                img, pred = x.clone(), r["masks"][:, 0].contiguous()
+                _, counts = _ev.label_counts(pred, gt, im.contiguous(), img, pred)      # functions.py:3739-3747 in one pass
+                mk = pred[..., None]
+                sel = torch.nonzero(torch.tensor([plan[i][3] for i in idx], device="cuda")).flatten()
+                if sel.numel():      # functions.py:3756-3757
+                    o, om = augment_batch(img[sel].contiguous(), mk[sel].contiguous(), _aug_params(prm, [i for i in idx if plan[i][3]]))
+                    img[sel], mk[sel] = o, om
+                img_np, mk_np = img.cpu().numpy(), mk.cpu().numpy()
+                jobs = []
+                for row, i in enumerate(idx):
+                    out_name = f"{names[i][:-4]}_aug_{nl}.png"
+                    loop_rows[i] = (out_name, round(_ev.iou_multi_unique_from_counts(counts[row], "pred"), 4))
+                    jobs.append((os.path.join(iout, out_name), img_np[row]))
+                    jobs.append((os.path.join(mout, out_name), mk_np[row, :, :, 0]))
+                F.write_pngs_async(jobs)      # on the writer pool: the next batch's decode, network pass and augmentation run meanwhile
+            rows += [loop_rows[i] for i in range(len(names))]
+    F.flush_writes()
+    with open(os.path.join(main_output_path, "labels.csv"), "a", encoding="utf-8", newline="") as f:
+        wr = csv.writer(f, delimiter=";")
+        for row in rows:
+            wr.writerow(row)
+
+
+def _scalar_evalnet_input_b(model, ids, num_classes):
+    """input B of a get_evalnet model for class-id masks u8 [N,H,W,1]: the ids themselves where the net expands them on the device,
+    else the explicit 0 / 1 stack"""
+    if model.plan.cb != num_classes or model.n_heads != 1 or model.plan.n_out != 1:
+        raise ValueError("needs a get_evalnet(..., inputB_channels=num_classes) model")
+    return ids if model.plan.b_onehot else _one_hot_u8(ids, num_classes).contiguous()
+
+
+def train_evalnet_multiclass(model, train_main_path, val_main_path, filepath_h5, batch_size, num_classes, epochs, seed=None):
+    """functions.py:4509-4552: train_evalnet_ISIC_2018's loop (loss 'mean_squared_error', best epoch by val_mean_absolute_error,
+    len // batch_size steps) with the masks read as class ids and fed as one-hot stacks (generate_images_batch_multiclass); images of
+    any size.  Returns (mse, mae) of the best model on the validation generator."""
+    F = _F()
+
+    def load(main_path):
+        xa, ids, y = _load_binary_evalnet_set(main_path, pool)
+        return xa, _scalar_evalnet_input_b(model, ids, num_classes), y
+
+    kind = ("scalar_multi", num_classes, bool(model.plan.b_onehot))
+    with F._pool() as pool:
+        tr = _cached_evalnet_set(kind, train_main_path, lambda: load(train_main_path))
+        va = _cached_evalnet_set(kind, val_main_path, lambda: load(val_main_path))
+    return _fit_evalnet(model, tr, va, filepath_h5, batch_size, epochs, _mse_mae_evaluator(batch_size), 1, seed)
+
+
+def _scalar_selection(evalnets, h, w, c, num_classes, images_path, mask_paths, main_output_path, threshold, last_gen_main_path, rgb):
+    """the body of the two writers below: the candidate with the best (mean) predicted IoU, kept if it reaches the threshold"""
+    from .evalnet import SELECT_IOU
+    iout, mout = os.path.join(main_output_path, "images"), os.path.join(main_output_path, "masks")
+    os.makedirs(iout, exist_ok=True)
+    os.makedirs(mout, exist_ok=True)
+    _copy_last_generation(last_gen_main_path, main_output_path, ("images", "masks"))
+    class_ids = _takes_class_ids(evalnets)
+
+    def emit(name, chosen):
+        shutil.copy(os.path.join(images_path, name), os.path.join(iout, name))
+        return [(os.path.join(mout, name), chosen.reshape(h, w))]
+    load = _mask_candidates(mask_paths, mout, h, w, class_ids)
+    if not class_ids:      # models that take the one-hot stack (functions.py:5217)
+        ids = load
+
+        def load(pool, chunk):
+            xb, cand, counts = ids(pool, chunk)
+            return _one_hot_u8(xb, num_classes), cand, counts
+    _run_selection(evalnets, images_path, c, (not rgb) and c == 3, threshold, load, emit, SELECT_IOU)
+
+
+def create_training_data_for_segnet_multiclass(evalnet_model, h, w, c, num_classes, images_path, mask_paths, main_output_path, threshold,
+                                               last_gen_main_path='', rgb=True):
+    """functions.py:5158-5231: images/ (the file, copied) and masks/ (the class-id candidate with the best predicted IoU) of every
+    unlabeled image whose best predicted IoU reaches `threshold`."""
+    _scalar_selection([evalnet_model], h, w, c, num_classes, images_path, mask_paths, main_output_path, threshold, last_gen_main_path, rgb)
+
+
+def create_training_data_for_segnet_with_ensemble_multiclass(evalnets, h, w, c, num_classes, images_path, mask_paths, main_output_path,
+                                                             threshold, last_gen_main_path='', rgb=True):
+    """functions.py:5236-5317: as the writer above with the mean of the EvalNets' predicted IoUs."""
+    _scalar_selection(list(evalnets), h, w, c, num_classes, images_path, mask_paths, main_output_path, threshold, last_gen_main_path, rgb)
+
+
+def num_augs_from_iou_f32(pred_iou, min_threshold, max_threshold):
+    """functions.py:5816-5825 as numpy evaluates it: pred_iou is predict()'s float32 [1,1] array, so the Python thresholds and the
+    step are rounded to float32, and difference and quotient are float32 operations"""
+    f = np.float32
+    v, step = f(pred_iou), f((max_threshold - min_threshold) / 5)
+    if v > f(max_threshold):
+        n = 5
+    elif v > f(min_threshold):
+        n = 1 + int((v - f(min_threshold)) / step)
+    else:
+        n = 1
+    return min(n, 5)
+
+
+def _write_augmented(chunk, x, m, n_augs, draw_kw, iout, mout):
+    """copies j = 0 .. n_augs[i] - 1 of every pair of a chunk, `{stem}___{j}.png`: copy j of all the images that get one is one
+    augment_batch call -> the PNG jobs"""
+    n_augs = torch.tensor(n_augs, device="cuda")
+    jobs = []
+    for j in range(5):
+        sel = torch.nonzero(n_augs > j).flatten()
+        if not sel.numel():
+            break
+        o, om = augment_batch(x[sel].contiguous(), m[sel].contiguous(), draw_params(int(sel.numel()), **draw_kw))
+        o, om = o.cpu().numpy(), om.cpu().numpy()
+        for row, i in enumerate(sel.tolist()):
+            name = f"{chunk[i][:-4]}___{j}.png"
+            jobs.append((os.path.join(iout, name), o[row]))
+            jobs.append((os.path.join(mout, name), om[row, :, :, 0]))
+    return jobs
+
+
+def create_augment_images_and_masks_with_evalnet_multiclass(evalnet_model, h, w, c, num_classes, min_threshold, max_threshold,
+                                                            main_input_path, main_output_path, brightness_range_alpha=(0.6, 1.4),
+                                                            brightness_range_beta=(-20, 20), max_blur=3, max_noise=20,
+                                                            free_rotation=False, rgb=True):
+    """functions.py:5762-5831: 1..5 augmented copies `{stem}___{j}.png` of every pseudo-labelled pair, the number growing with the
+    IoU the one EvalNet predicts for (image, class-id mask)."""
+    F = _F()
+    flip = (not rgb) and c == 3      # rgb=False (functions.py:3611 ff.): the nets see the file's channels in OpenCV's order (BGR)
+    iin, min_ = os.path.join(main_input_path, "images"), os.path.join(main_input_path, "masks")
+    iout, mout = os.path.join(main_output_path, "images"), os.path.join(main_output_path, "masks")
+    os.makedirs(iout, exist_ok=True)
+    os.makedirs(mout, exist_ok=True)
+    mine = F.shard_list(os.listdir(iin))
+    native = isinstance(evalnet_model, EvalNet)
+    draw_kw = dict(brightness_range_alpha=brightness_range_alpha, brightness_range_beta=brightness_range_beta,
+                   max_blur=max_blur, max_noise=max_noise, free_rotation=free_rotation)
+    with F._pool() as pool:
+        for s in range(0, len(mine), F.INFER_BATCH):
+            chunk = mine[s:s + F.INFER_BATCH]
+            x = torch.from_numpy(F.read_png_stack(pool, [os.path.join(iin, n) for n in chunk], c)).cuda()
+            m = torch.from_numpy(F.read_png_stack(pool, [os.path.join(min_, n) for n in chunk], 1)).cuda()
+            xin = x.flip(-1).contiguous() if flip else x
+            if native:
+                ious = evalnet_model.predict_device(xin, _scalar_evalnet_input_b(evalnet_model, m, num_classes))[:, 0].cpu().numpy()
+            else:      # anything with Keras' .predict: the repeated call of the reference, the one-hot stack as it builds it
+                ious = np.asarray(evalnet_model.predict([xin.cpu().numpy(), _one_hot_u8(m, num_classes).cpu().numpy().astype(np.int32)]),
+                                  dtype=np.float32).reshape(-1)
+            n_augs = [num_augs_from_iou_f32(v, min_threshold, max_threshold) for v in ious]
+            F.write_pngs_async(_write_augmented(chunk, x, m, n_augs, draw_kw, iout, mout))
+    F.flush_writes()
+    if F._dist():
+        F._dist().barrier()

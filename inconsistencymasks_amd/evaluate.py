@@ -57,6 +57,48 @@ def pa_iou_from_counts(c, n_pix):
     return pa, total / len(classes)
 
 
+def label_counts(pred, gt, im=None, image=None, pred_blocked=None):
+    """imk_label_counts: pred, gt [B,H,W] u8 cuda class ids; im [B,H,W] u8 cuda or None -- where im > 0 the prediction counts as
+    class 0, `image` [B,H,W,c] u8 cuda (c = 1 or 3), if given, is zeroed there IN PLACE, and `pred_blocked` receives the blocked
+    prediction: a uint8 tensor [B,H,W] (it may be `pred` itself), or True for a new one.
+    -> (blocked prediction cuda | None, counts [B,4,256] int64 numpy: #(gt == v), #(p' == v), #(gt == v & p' == v), #(gt == v & im == 0))."""
+    assert pred.is_cuda and pred.dtype == torch.uint8 and pred.dim() == 3 and pred.is_contiguous()
+    assert gt.is_cuda and gt.dtype == torch.uint8 and gt.shape == pred.shape and gt.is_contiguous()
+    B, H, W = pred.shape
+    c = 0
+    if im is not None:
+        assert im.is_cuda and im.dtype == torch.uint8 and im.shape == pred.shape and im.is_contiguous()
+    if image is not None:
+        assert image.is_cuda and image.dtype == torch.uint8 and image.dim() == 4 and image.shape[:3] == pred.shape and image.is_contiguous()
+        c = image.shape[3]
+    if pred_blocked is True:
+        pred_blocked = torch.empty_like(pred)
+    if pred_blocked is not None:
+        assert pred_blocked.is_cuda and pred_blocked.dtype == torch.uint8 and pred_blocked.shape == pred.shape and pred_blocked.is_contiguous()
+    counts = torch.empty((B, 4, 256), dtype=torch.int64, device=pred.device)
+    check(lib.imk_label_counts(pred.data_ptr(), gt.data_ptr(), im.data_ptr() if im is not None else None,
+                               image.data_ptr() if image is not None else None, c, B, H, W,
+                               pred_blocked.data_ptr() if pred_blocked is not None else None, counts.data_ptr(), _stream()),
+          "imk_label_counts")
+    return pred_blocked, counts.cpu().numpy()
+
+
+def iou_multi_unique_from_counts(counts, unique_of):
+    """get_IoU_multi_unique (functions.py:1791-1816) from one image's label counts [4,256]: the mean, over the classes present in one of
+    the two maps, of inter / (union + 1e-7).  unique_of names the map whose classes count: "gt", or "pred" -- the blocked prediction,
+    class 0 included as soon as one pixel is blocked.  The training-data writers call get_IoU_multi_unique(mask_gray, mask_pred), the
+    ground truth in the `pred` seat (functions.py:3550, 3747): their labels are unique_of="pred"."""
+    if unique_of not in ("pred", "gt"):
+        raise ValueError(f"unique_of must be 'pred' or 'gt', got {unique_of!r}")
+    c = np.asarray(counts, dtype=np.int64)
+    n_gt, n_pr, n_both = c[0], c[1], c[2]
+    iou_list = []
+    for v in np.nonzero(n_pr if unique_of == "pred" else n_gt)[0]:      # np.unique: ascending
+        union = n_gt[v] + n_pr[v] - n_both[v]
+        iou_list.append(n_both[v] / (union + 1e-7))
+    return sum(iou_list) / len(iou_list)
+
+
 def soft_sums(probs, gt, mode):
     """Validation-monitor reductions on the device (imk_eval_soft_sums), deterministic.
     mode 0: probs [..., K] f32, gt [...] u8 class ids -> float64 numpy [3, K] = (sum [gt == k] p_k, sum [gt == k], sum p_k)

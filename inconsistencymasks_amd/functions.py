@@ -1975,6 +1975,12 @@ from .evalnet_functions import (compute_classwise_detection, compute_classwise_d
                                 create_training_data_for_segnet_with_miou_ensemble_multiclass, load_evalnet, num_augs_from_miou,
                                 save_evalnet, train_evalnet_ISIC_2018, train_evalnet_miou_model_hela,
                                 train_evalnet_miou_model_multiclass)
+# the scalar-IoU multiclass EvalNet family (functions.py:3496-3567, 3673-3769, 4360-4395, 4509-4552, 5158-5317, 5762-5831)
+from .evalnet_functions import (compute_classwise_confluence, create_augment_images_and_masks_with_evalnet_multiclass,  # noqa: E402,F401
+                                create_training_data_evalnet_im_multiclass, create_training_data_evalnet_multiclass,
+                                create_training_data_for_segnet_multiclass,
+                                create_training_data_for_segnet_with_ensemble_multiclass, get_confluence_binary,
+                                num_augs_from_iou_f32, train_evalnet_multiclass)
 from .consistency import (train_hela_consistency_loss, train_ISIC_2018_consistency_loss,  # noqa: E402,F401
                           train_multiclass_consistency_loss)
 # the depth-map (regression) family (functions.py:36-48, 320-364, 903-927, 1051-1073, 1345-1384, 6155-6177)
